@@ -25,6 +25,10 @@ Extra objects in the line:
   cpu_baseline  the oracle (PyTorch-CPU restatement of the reference TF graph, TF1 dense Adam)
                 timed on the host cores on a bounded sample of the same workload (rank 0, N=1)
   recommend     items-scored/sec of full-catalog top-k scoring (the metric's second half)
+
+`--dump-outputs DIR` (single-GPU DeepFM step) writes what the last timed step computed as DIR/<name>.npy: the loss, the dense
+parameters and a seeded sample of the embedding rows its batch touched.  Inputs and initial weights are seeded, so two builds
+run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -273,8 +277,10 @@ def bench_train(args, rank, world, dev):
         net.enable_graph(True)                 # first 2 steps eager, third captured, then replays
     row_sharded = (world > 1 or args.force_sharded) and args.parallel == "row"
 
+    last = {}
+
     def one_step():
-        cur = pool.next()
+        cur = last["batch"] = pool.next()
         if row_sharded:      # the next (resident) batch's exchange plan is built beside this step
             return net.train_step(*cur, next_idx=pool.peek(0)[0])
         return net.train_step(*cur)
@@ -303,6 +309,8 @@ def bench_train(args, rank, world, dev):
     dt = time.perf_counter() - t0
     clk.mark(1)
     ops.TIMER.disable()
+    if args.dump_outputs:        # before anything below trains the net further
+        dump_train_outputs(args.dump_outputs, net, last["batch"][0], loss)
     final_loss = float(loss)
     from librecommender_amd.layers.tail import check_all as _tail_check
 
@@ -472,6 +480,32 @@ def bench_train(args, rank, world, dev):
     return result, cfg, host
 
 
+DUMP_ROWS = 8192                # embedding rows of the last timed batch sampled into the dump
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_train_outputs(out_dir, net, idx, loss):
+    """What the last timed step computed, as float32 / float64 `.npy` files under `out_dir`: the loss it returned, the dense
+    parameters after its Adam update, and a fixed seeded sample of DUMP_ROWS distinct embedding rows its batch touched (rows,
+    linear weights and their global row ids).  The inputs are seeded, so two builds given the same arguments can be compared
+    file for file."""
+    rows = torch.unique(idx.reshape(-1).to(torch.int64)).cpu().numpy()       # sorted
+    if rows.size > DUMP_ROWS:
+        rows = np.sort(np.random.default_rng(0).choice(rows, DUMP_ROWS, replace=False))
+    sel = torch.from_numpy(rows).to(net.tables.embed.device)
+    arrays = {"loss": np.asarray([float(loss)], dtype=np.float64),
+              "dense_params": net.P.flat.detach().cpu().numpy().astype(np.float32),
+              "embed_row_ids": rows.astype(np.float64),
+              "embed_rows": net.tables.embed.index_select(0, sel).cpu().numpy().astype(np.float32)}
+    if net.tables.lin is not None:
+        arrays["linear_rows"] = net.tables.lin.index_select(0, sel).reshape(-1).cpu().numpy().astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"dump of {total} bytes exceeds {DUMP_LIMIT_BYTES}"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def bench_f32_chain(args, cfg, dev):
     """The same step with the first layer on the EXACT f32 fma chain (`ops.set_l1_arith("f32_chain")`: csrc/deepfm_l1.hip,
     rounds 1-4's arithmetic), hipGraph replays on fresh batches — timed beside the default so the line shows what the
@@ -624,35 +658,20 @@ def bench_cpu_baseline(cfg, host, seconds_budget=25.0):
 
 
 def bench_recommend_cpu_baseline(seconds_budget=12.0):
-    """CPU baseline of the recommend leg: `recommend_from_embedding` + `rank_recommendations`
-    (recommendation/recommend.py:57-78, ranking.py:10-56) on the host cores — the reference's own
-    functions where the checkout is present (build container), the numpy restatement (oracle/ops_np.py)
-    on the GPU box where it is not.  Bounded sample: 128-dim embeddings, 1 M items, users in chunks of 64
-    until the budget is spent; items-scored/s is size-independent for this O(B*N*D) + O(B*N) path, the
-    12.5 M-item figure is a linear extrapolation."""
-    from oracle import ref_loader
+    """CPU baseline of the recommend leg: the numpy restatement (oracle/ops_np.py) of `recommend_from_embedding` +
+    `rank_recommendations` (recommendation/recommend.py:57-78, ranking.py:10-56 of the reference) on the host cores.
+    Bounded sample: 128-dim embeddings, 1 M items, users in chunks of 64 until the budget is spent; items-scored/s is
+    size-independent for this O(B*N*D) + O(B*N) path, the 12.5 M-item figure is a linear extrapolation."""
+    from oracle import ops_np
 
     rng = np.random.default_rng(0)
     N, D, k, chunk = 1_000_000, 128, 100, 64
     I = rng.standard_normal((N, D)).astype(np.float32)
     consumed = {u: sorted(rng.integers(0, N, 50).tolist()) for u in range(chunk)}
     kind = "port"
-    if ref_loader.available():
-        try:
-            ref_loader.load()
-            from libreco.recommendation.ranking import rank_recommendations as ref_rank
 
-            def run(U, users):
-                preds = U @ I.T                                              # recommend.py:66-68
-                return ref_rank("ranking", users, preds, k, N, consumed, True, False)
-            kind = "reference"
-        except Exception:  # noqa: BLE001
-            kind = "port"
-    if kind == "port":
-        from oracle import ops_np
-
-        def run(U, users):          # recommend.py:66-68 + the reference's partition-based selection
-            return ops_np.rank_recommendations_partition(users, U @ I.T, k, N, consumed, True)
+    def run(U, users):          # recommend.py:66-68 + the reference's partition-based selection
+        return ops_np.rank_recommendations_partition(users, U @ I.T, k, N, consumed, True)
     users = list(range(chunk))
     t_total, n_users = 0.0, 0
     while t_total < seconds_budget and n_users < 4096:
@@ -861,7 +880,14 @@ def main():
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="gloo = functional check of the N>1 path with ranks sharing one GPU "
                          "(collectives staged through host; not a measurement)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, dense parameters, a seeded sample of the embedding rows "
+                         "its batch touched) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if args.dump_outputs and (args.workload != "deepfm" or args.gpus > 1 or args.force_sharded):
+        raise SystemExit("--dump-outputs covers the single-GPU DeepFM training step (--workload deepfm, --gpus 1)")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -1025,14 +1051,13 @@ def _guard(fn):
 
 
 def _reference_note():
-    """Where the CPU baselines come from on this box (`cpu_baseline.kind`): the reference checkout exists only in the build
-    container; its own functions were timed there (8 cores) and the numbers are committed next to this file."""
-    from oracle import ref_loader
-
-    note = {"present": bool(ref_loader.available()),
-            "meaning": "kind 'reference' = the reference's own functions ran on this box; kind 'port' = the oracle restatement "
-                       "(the checkout /root/reference is absent here; TensorFlow is absent everywhere, so the FM / DeepFM / DIN / "
-                       "TwoTower graphs are always the restatement)"}
+    """Where the CPU baselines come from (`cpu_baseline.kind`): the benchmark never reads the reference checkout, so every
+    baseline it times is the oracle restatement; the reference's own functions were timed once next to its checkout
+    (8 cores) and those numbers are committed under profiles/."""
+    note = {"present": False,
+            "meaning": "kind 'port' = the oracle restatement, timed on this host (the benchmark does not read the reference "
+                       "checkout; TensorFlow is absent everywhere, so the FM / DeepFM / DIN / TwoTower graphs are always the "
+                       "restatement)"}
     try:
         with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", "r04_cpu_reference_baselines.json")) as fh:
             note["reference_run_build_container"] = json.load(fh)

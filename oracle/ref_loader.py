@@ -11,7 +11,10 @@ STUBS = Path(__file__).resolve().parent / "_stubs"
 
 
 def available() -> bool:
-    return (REFERENCE / "libreco" / "__init__.py").exists()
+    try:
+        return (REFERENCE / "libreco" / "__init__.py").exists()
+    except OSError:         # a checkout the current user may not read counts as absent
+        return False
 
 
 def load():
