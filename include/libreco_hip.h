@@ -846,6 +846,37 @@ int lr_pair_mlp_sb_f32(const float* P, int64_t B, const float* Q, int64_t N, int
                        const float* b2, int H2, const float* v3, float c3, float* out, int64_t ld_out,
                        int accumulate, lr_stream_t stream);
 
+/* ----------------------------------------------------------------------------------
+ * Alternating least squares (csrc/als.hip) — replaces the CPU solver of ALS, `als_update` with `_least_squares`
+ * (libreco/algorithms/_als.pyx:99-167, per-row `sposv`) and `_least_squares_cg` (_als.pyx:170-268, cg_steps CG iterations
+ * from the current row), and the `initialA` Gram of both (_als.pyx:116-120, 189-193).  K in 1..128 (lr_als_supported).
+ *   lr_als_gram_f32        G0 [K, K] = Y^T Y + reg I over the N rows of Y (implicit != 0) or reg I (explicit); the Gram is
+ *                          split over workgroups into K x K partials (ws: lr_als_gram_ws_bytes(N, K)) summed in a fixed order.
+ *   lr_als_plan_params     out3 = {light cap, heavy degree, chunk}: rows of degree <= light cap are solved one per wave from
+ *                          LDS (CG only), rows of degree > heavy degree are formed in `chunk`-interaction slabs over many
+ *                          workgroups, the rest one per workgroup.  Host-only.
+ *   lr_als_ws_bytes        slab workspace of a half-sweep whose heavy rows hold n_chunks chunks (host-only).
+ *   lr_als_half_sweep_f32  every row m of X [rows, K] (in place) against Y: A_m = G0 + sum_i w_i y_i y_i^T, b_m = sum_i
+ *                          beta_i y_i over the CSR row (int64 rowptr, int32 col, f32 val); implicit: w = val - 1, beta = val
+ *                          (val = the confidence alpha r + 1); explicit: w = 1, beta = val.  use_cg: cg_steps CG iterations
+ *                          from x (continue when r.r < 1e-10, break when the new r.r < 1e-10), else the Cholesky solve; a
+ *                          non-positive pivot k sets fail[m] = k + 1 and leaves row m unchanged (fail: int32 [rows], the
+ *                          caller zeroes it; may be NULL with use_cg).  `plan` (int32): light rows [n_light], medium rows
+ *                          [n_medium], heavy rows [n_heavy], chunk_begin [n_heavy + 1] (prefix sums of ceil(deg / chunk)),
+ *                          chunk_row [n_chunks] (the heavy slot of each chunk); every row listed exactly once.
+ *                          stage_mask: 1 light, 2 medium, 4 heavy slabs, 8 heavy solves (15 = the whole sweep; the parts
+ *                          exist for per-kernel timing, 8 needs 4 first).  No atomics: identical bits run to run. */
+int lr_als_supported(int K);
+int lr_als_plan_params(int K, int32_t* out3);
+size_t lr_als_ws_bytes(int64_t n_chunks, int K);
+size_t lr_als_gram_ws_bytes(int64_t N, int K);
+int lr_als_gram_f32(const float* Y, int64_t N, int K, float reg, int implicit, float* G0, void* ws, size_t ws_bytes,
+                    lr_stream_t stream);
+int lr_als_half_sweep_f32(const int64_t* rowptr, const int32_t* col, const float* val, int64_t rows, float* X,
+                          const float* Y, int K, const float* G0, int implicit, int use_cg, int cg_steps,
+                          const int32_t* plan, int64_t n_light, int64_t n_medium, int64_t n_heavy, int64_t n_chunks,
+                          int32_t* fail, void* ws, size_t ws_bytes, int stage_mask, lr_stream_t stream);
+
 /* Measurement probe (scripts/mfma_peak.py): iters x 8 back-to-back v_mfma_f32_32x32x2_f32 per wave on
  * 256 x waves_per_simd workgroups — the f32 MFMA rate the chip sustains at the clock it holds under that load. */
 int lr_mfma_f32_probe(int iters, int waves_per_simd, float* out, lr_stream_t stream);

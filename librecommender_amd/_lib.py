@@ -193,6 +193,13 @@ SIGNATURES = {
     "lr_topk_merge_f32": (_int, [_p, _p, _int, _i64, _int, _p, _p, _p]),
     "lr_spmm_csr_f32": (_int, [_p, _p, _p, _i64, _p, _int, _p, _p, _p]),
     "lr_pair_dot_f32": (_int, [_p, _i64, _p, _i64, _int, _p, _p, _i64, _p, _p]),
+    "lr_als_supported": (_int, [_int]),
+    "lr_als_plan_params": (_int, [_int, _p]),
+    "lr_als_ws_bytes": (_sz, [_i64, _int]),
+    "lr_als_gram_ws_bytes": (_sz, [_i64, _int]),
+    "lr_als_gram_f32": (_int, [_p, _i64, _int, _f32, _int, _p, _p, _sz, _p]),
+    "lr_als_half_sweep_f32": (_int, [_p, _p, _p, _i64, _p, _p, _int, _p, _int, _int, _int, _p, _i64, _i64, _i64, _i64,
+                                     _p, _p, _sz, _int, _p]),
 }
 
 _lib = None

@@ -1,3 +1,4 @@
+from .als import ALS
 from .din import DIN
 from .fm import FM, DeepFM
 from .lightgcn import LightGCN
@@ -8,4 +9,4 @@ from .two_tower import TwoTower
 from .youtube_ranking import YouTubeRanking
 from .youtube_retrieval import YouTubeRetrieval
 
-__all__ = ["DIN", "DeepFM", "FM", "LightGCN", "NGCF", "SIM", "Transformer", "TwoTower", "YouTubeRanking", "YouTubeRetrieval"]
+__all__ = ["ALS", "DIN", "DeepFM", "FM", "LightGCN", "NGCF", "SIM", "Transformer", "TwoTower", "YouTubeRanking", "YouTubeRetrieval"]

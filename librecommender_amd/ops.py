@@ -1429,3 +1429,109 @@ def csr_laplacian(users: torch.Tensor, items: torch.Tensor, n_users: int, n_item
     if nnz == 2 * E:
         return rowptr, col, val, tperm
     return rowptr, col[:nnz].clone(), val[:nnz].clone(), (tperm[:nnz].clone() if want_tperm else None)
+
+
+# --------------------------------------------------------------------------------------
+# ALS (csrc/als.hip)
+# --------------------------------------------------------------------------------------
+def als_supported(K: int) -> bool:
+    return bool(_lib.load().lr_als_supported(int(K)))
+
+
+def _als_check_k(K: int) -> None:
+    if not als_supported(K):
+        raise ValueError(f"ALS supports embed_size 1..128 (the per-row K x K system is solved in LDS), got {K}")
+
+
+class AlsPlan:
+    """Degree plan of one CSR orientation (the rows of one half-sweep), built once per `fit`: the CSR does not change
+    between epochs.  Light rows are solved one per wave from LDS, medium rows one per workgroup, heavy rows are cut into
+    fixed chunks whose partial systems are reduced in chunk order (lr_als_plan_params gives the degree limits).  Owns the
+    slab workspace of the heavy rows."""
+
+    def __init__(self, rowptr: torch.Tensor, K: int):
+        _req(rowptr, torch.int64, "rowptr", 1)
+        _als_check_k(K)
+        import ctypes as C
+
+        lim = (C.c_int32 * 3)()
+        check(_lib.load().lr_als_plan_params(int(K), lim), "lr_als_plan_params")
+        self.light_cap, self.heavy_deg, self.chunk = int(lim[0]), int(lim[1]), int(lim[2])
+        self.rowptr_ptr, self.rows, self.K = rowptr.data_ptr(), rowptr.numel() - 1, int(K)
+        deg = rowptr[1:] - rowptr[:-1]
+        light = torch.nonzero(deg <= self.light_cap).flatten()
+        medium = torch.nonzero((deg > self.light_cap) & (deg <= self.heavy_deg)).flatten()
+        heavy = torch.nonzero(deg > self.heavy_deg).flatten()
+        n_ch = torch.div(deg[heavy] + self.chunk - 1, self.chunk, rounding_mode="floor")
+        begin = torch.zeros(heavy.numel() + 1, dtype=torch.int64, device=rowptr.device)
+        begin[1:] = torch.cumsum(n_ch, 0)
+        chunk_row = torch.repeat_interleave(torch.arange(heavy.numel(), device=rowptr.device), n_ch)
+        self.plan = torch.cat([light, medium, heavy, begin, chunk_row]).to(torch.int32).contiguous()
+        self.n_light, self.n_medium, self.n_heavy = light.numel(), medium.numel(), heavy.numel()
+        self.n_chunks = chunk_row.numel()
+        need = _lib.load().lr_als_ws_bytes(self.n_chunks, self.K)
+        self.ws = torch.empty(max(need, 256), dtype=torch.uint8, device=rowptr.device)
+
+    def matches(self, rowptr: torch.Tensor, K: int) -> bool:
+        return rowptr.data_ptr() == self.rowptr_ptr and rowptr.numel() - 1 == self.rows and int(K) == self.K
+
+
+def als_plan(rowptr: torch.Tensor, K: int) -> AlsPlan:
+    return AlsPlan(rowptr, K)
+
+
+def als_gram(Y: torch.Tensor, reg: float, implicit: bool, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """G0 = Y^T Y + reg I (implicit) or reg I (explicit), [K, K] f32; the Gram's partials are summed in a fixed order."""
+    _req(Y, torch.float32, "Y", 2)
+    N, K = Y.shape
+    _als_check_k(K)
+    if out is None:
+        out = torch.empty((K, K), dtype=torch.float32, device=Y.device)
+    else:
+        _req(out, torch.float32, "out", 2)
+        if tuple(out.shape) != (K, K):
+            raise ValueError("out must be [K, K]")
+    need = _lib.load().lr_als_gram_ws_bytes(N, K) if implicit else 0
+    key = (Y.device, "als_gram")
+    ws = _WS_CACHE.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _WS_CACHE[key] = torch.empty(max(need, 256), dtype=torch.uint8, device=Y.device)
+    _call("lr_als_gram_f32", _ptr(Y), N, K, float(reg), 1 if implicit else 0, _ptr(out), _ptr(ws), ws.numel(), _stream())
+    return out
+
+
+def als_half_sweep(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, X: torch.Tensor, Y: torch.Tensor,
+                   G0: torch.Tensor, implicit: bool, use_cg: bool, plan: AlsPlan, cg_steps: int = 3,
+                   fail: Optional[torch.Tensor] = None, stage_mask: int = 15) -> Optional[torch.Tensor]:
+    """Update every row of X in place against Y (one ALS half-sweep, `_als.pyx:als_update`).  `val` holds the confidence
+    alpha r + 1 (implicit) or the rating (explicit).  The direct solver returns the per-row failure words (int32 [rows],
+    nonzero where a pivot was not positive: that row is left unchanged); `fail` may be passed in (it is zeroed here)."""
+    _req(rowptr, torch.int64, "rowptr", 1)
+    _req(col, torch.int32, "col", 1)
+    _req(val, torch.float32, "val", 1)
+    _req(X, torch.float32, "X", 2)
+    _req(Y, torch.float32, "Y", 2)
+    _req(G0, torch.float32, "G0", 2)
+    rows, K = X.shape
+    _als_check_k(K)
+    if Y.shape[1] != K or tuple(G0.shape) != (K, K):
+        raise ValueError("X, Y and G0 must share the embedding width K")
+    if rowptr.numel() != rows + 1 or col.numel() != val.numel():
+        raise ValueError("the CSR must have one row per row of X and one value per column index")
+    if not plan.matches(rowptr, K):
+        raise ValueError("the AlsPlan was made for another CSR (rowptr / K differ)")
+    if cg_steps < 0:
+        raise ValueError("cg_steps must be non-negative")
+    if not use_cg:
+        if fail is None:
+            fail = torch.zeros(rows, dtype=torch.int32, device=X.device)
+        else:
+            _req(fail, torch.int32, "fail", 1)
+            if fail.numel() != rows:
+                raise ValueError("fail holds one word per row")
+            fail.zero_()
+    _call("lr_als_half_sweep_f32", _ptr(rowptr), _ptr(col), _ptr(val), rows, _ptr(X), _ptr(Y), K, _ptr(G0),
+          1 if implicit else 0, 1 if use_cg else 0, int(cg_steps), _ptr(plan.plan), plan.n_light, plan.n_medium,
+          plan.n_heavy, plan.n_chunks, _ptr(None if use_cg else fail), _ptr(plan.ws), plan.ws.numel(), int(stage_mask),
+          _stream())
+    return None if use_cg else fail
