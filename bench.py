@@ -20,11 +20,17 @@ size on one GPU (bench_workloads.py); the default (`deepfm`) is the configuratio
 `--workload twotower --gpus N` (cfg 4: table row-sharded, global in-batch softmax) and `--workload lightgcn --gpus N`
 (cfg 5: node table and Laplacian row-partitioned) are the strong-scaling legs of the 8-GPU configurations.
 
-Extra objects in the line:
-  roofline      dominant hand-written kernel of the step, algorithmic bytes / HIP-event time
+A plain DeepFM run sets up, warms up, times the steps and prints the headline line (with the loss and the shader clock
+of the timed region in `config`), nothing more.  `--full` measures the rest of the picture after it, into the same line:
+  roofline      dominant hand-written kernel of the step, algorithmic bytes / HIP-event time (+ `kernels`,
+                `roofline_scatter`, `roofline_step`; a graphed step is timed kernel by kernel in an eager pass of its own)
+  steady_state  ms/step over >= 1 s of further steps (`--steady-seconds`)
+  recommend     items-scored/sec of full-catalog top-k scoring (the metric's second half)
+  f32_chain, dense_adam   the step with the exact f32 first layer / with TF1's dense Adam over every table row
   cpu_baseline  the oracle (PyTorch-CPU restatement of the reference TF graph, TF1 dense Adam)
                 timed on the host cores on a bounded sample of the same workload (rank 0, N=1)
-  recommend     items-scored/sec of full-catalog top-k scoring (the metric's second half)
+  workloads     cfg 3 / 4 / 5 and the DeepFM full-catalogue ranking at full size on the same GPU (N=1)
+The `--no-*` options skip parts of it.  `--workload` lines are unchanged by `--full`.
 
 `--dump-outputs DIR` (single-GPU DeepFM step) writes what the last timed step computed as DIR/<name>.npy: the loss, the dense
 parameters and a seeded sample of the embedding rows its batch touched.  Inputs and initial weights are seeded, so two builds
@@ -320,6 +326,68 @@ def bench_train(args, rank, world, dev):
         tt = torch.tensor([dt], device=dev if args.backend == "nccl" else "cpu", dtype=torch.float64)
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         dt = float(tt.item())
+    ms = dt / args.steps * 1e3
+    l1_arith = getattr(net, "l1_arith", "f32_chain") if getattr(net, "fused_l1", False) or row_sharded else "f32_chain"
+    F = 2 + Fs
+    result = {
+        "metric": "train samples/sec", "value": round(B * world * args.steps / dt, 1),
+        "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": ("f32 (split-bf16 x6 MFMA products, f32 accumulate)" if l1_arith == "split_bf16" else "f32")
+                 if args.mlp_dtype == "fp32" else "f32 tables+FM, bf16 MLP GEMMs",
+        "data": "synthetic",
+        "config": {"workload": "DeepFM ranking train step, 1M users x 1M items x 200 sparse fields "
+                               "(10,000,200 sparse rows), embed_size=64, hidden=(128,64,32), "
+                               "Zipf(1.05) ids" if not args.small else "DeepFM small (smoke)",
+                   "per_gpu_batch": B, "global_batch": B * world, "fields": F, "embed_size": K,
+                   "table_rows": n_rows, "optimizer": "row-wise Adam on the touched embedding rows (TF1 moves every row: equal at step 1, "
+                                "diverges afterwards; dense_adam=True reproduces TF1) + dense Adam (MLP)",
+                   "first_layer": ("lookup fused with the first Dense layer; " + (
+                                       "its three contractions as six-term split-bf16 MFMA products with f32 accumulation (every f32 operand split "
+                                       "exactly into three bf16 values; as close to fp64 as the f32 fma chain: tests/test_l1_split_bf16_gpu.py; the "
+                                       "exact f32 chain stays selectable: LIBRECO_L1_ARITH=f32_chain, timed beside as f32_chain_ms_per_step by --full)"
+                                       if l1_arith == "split_bf16" else "f32 MFMA (exact f32 fma chain)"))
+                                  if (getattr(net, "fused_l1", False) or getattr(net, "field_row_start", None) is not None)
+                                  else "materialised deep_embed + library GEMM",
+                   "parallelism": parallelism, "final_loss": round(final_loss, 5),
+                   "stream": "a fresh batch every step, drawn on the device before the timed region (exact Zipf(1.05) ids, "
+                             "Bernoulli(0.5) labels); no batch is trained on twice",
+                   "launch": "one hipGraph replay per step" if graphed else "eager launches",
+                   "shader_clock_mhz": clock_mhz, "realtime_counter_mhz": round(clk.rt_hz / 1e6, 2)},
+    }
+    if args.full:
+        result.update(step_kernel_figures(args, cfg, world, net, one_step, timed, graphed, first, ms))
+    if args.steady_seconds > 0 and world == 1:      # >= 1 s of steady-state replays next to the driver's short region
+        n = max(args.steps, int(args.steady_seconds / max(dt / args.steps, 1e-6)) + 1)
+        pool.ensure(n + 6)
+        if graphed:
+            net.enable_graph(True)
+            for s in range(4):
+                one_step()
+        barrier()
+        t1 = time.perf_counter()
+        for s in range(n):
+            loss_ss = one_step()
+        barrier()
+        result["steady_state"] = {"steps": n, "ms_per_step": round((time.perf_counter() - t1) / n * 1e3, 4),
+                                  "final_loss": round(float(loss_ss), 5), "distinct_batches": pool.cursor}
+        result["steady_ms_per_step"] = result["steady_state"]["ms_per_step"]
+        result["steady_steps"] = n
+        # (the driver's record keeps `config`, `roofline` and `cpu_baseline` whole and only the NAMES of other keys)
+        result["config"]["steady_ms_per_step"] = result["steady_ms_per_step"]
+        result["config"]["steady_steps"] = n
+    host = [host_batch(cfg, b) for b in first] if args.full else None       # (the CPU baseline's and dense-Adam leg's sample)
+    del net
+    return result, cfg, host
+
+
+def step_kernel_figures(args, cfg, world, net, one_step, timed, graphed, first, ms):
+    """`--full`: HIP-event times of the step's kernels and the rooflines built on them (`roofline`, `roofline_scatter`,
+    `roofline_step`, `kernels`).  A replayed graph cannot be timed kernel by kernel, so the graphed step pays an eager pass
+    of its own here, after the timed region."""
+    from librecommender_amd import ops
+
+    Fs, K, B = cfg["n_sparse_fields"], cfg["embed_size"], cfg["batch"]
     kernel_note = "HIP events around every C-ABI launch of the timed steps"
     if graphed:
         # events cannot be read back from inside a replayed graph: the same kernels are timed on the same
@@ -332,8 +400,6 @@ def bench_train(args, rank, world, dev):
         ops.TIMER.disable()
         kernel_note = (f"HIP events around every C-ABI launch in {min(args.steps, 10)} eager steps run after the timed "
                        f"region (the timed steps are hipGraph replays of the same launches)")
-    ms = dt / args.steps * 1e3
-    l1_arith = getattr(net, "l1_arith", "f32_chain") if getattr(net, "fused_l1", False) or row_sharded else "f32_chain"
     kern = ops.TIMER.summary()
     F = 2 + Fs
     H1 = cfg["hidden_units"][0]
@@ -412,43 +478,16 @@ def bench_train(args, rank, world, dev):
     roofline = roof(dom)
     scatter = next((n for n in ("lr_fm_rows_adam_f32", "lr_fm_embed_bwd_adam_f32", "lr_fm_rows_grad_f32",
                                 "lr_fm_embed_bwd_rows_f32") if n in kern), None)
-    result = {
-        "metric": "train samples/sec", "value": round(B * world * args.steps / dt, 1),
-        "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": ("f32 (split-bf16 x6 MFMA products, f32 accumulate)" if l1_arith == "split_bf16" else "f32")
-                 if args.mlp_dtype == "fp32" else "f32 tables+FM, bf16 MLP GEMMs",
-        "data": "synthetic",
-        "config": {"workload": "DeepFM ranking train step, 1M users x 1M items x 200 sparse fields "
-                               "(10,000,200 sparse rows), embed_size=64, hidden=(128,64,32), "
-                               "Zipf(1.05) ids" if not args.small else "DeepFM small (smoke)",
-                   "per_gpu_batch": B, "global_batch": B * world, "fields": F, "embed_size": K,
-                   "table_rows": n_rows, "optimizer": "row-wise Adam on the touched embedding rows (TF1 moves every row: equal at step 1, "
-                                "diverges afterwards; dense_adam=True reproduces TF1) + dense Adam (MLP)",
-                   "first_layer": ("lookup fused with the first Dense layer; " + (
-                                       "its three contractions as six-term split-bf16 MFMA products with f32 accumulation (every f32 operand split "
-                                       "exactly into three bf16 values; as close to fp64 as the f32 fma chain: tests/test_l1_split_bf16_gpu.py; the "
-                                       "exact f32 chain stays selectable: LIBRECO_L1_ARITH=f32_chain, timed beside as f32_chain_ms_per_step)"
-                                       if l1_arith == "split_bf16" else "f32 MFMA (exact f32 fma chain)"))
-                                  if (getattr(net, "fused_l1", False) or getattr(net, "field_row_start", None) is not None)
-                                  else "materialised deep_embed + library GEMM",
-                   "parallelism": parallelism, "final_loss": round(final_loss, 5),
-                   "stream": "a fresh batch every step, drawn on the device before the timed region (exact Zipf(1.05) ids, "
-                             "Bernoulli(0.5) labels); no batch is trained on twice",
-                   "launch": "one hipGraph replay per step" if graphed else "eager launches",
-                   "shader_clock_mhz": clock_mhz, "realtime_counter_mhz": round(clk.rt_hz / 1e6, 2)},
-        "roofline": roofline, "kernels": kinfo, "sum_kernel_ms": round(sum_kernel_ms, 4),
-        "kernel_timing": kernel_note,
-    }
+    out = {"roofline": roofline, "kernels": kinfo, "sum_kernel_ms": round(sum_kernel_ms, 4), "kernel_timing": kernel_note}
     if scatter is not None and scatter != dom:      # the gather+scatter-add+Adam kernel against the HBM roof
-        result["roofline_scatter"] = roof(scatter)
+        out["roofline_scatter"] = roof(scatter)
     # whole step against both roofs (SURVEY 8d cfg 2): 365 KB/sample of gather + scatter + Adam traffic and the
     # first layer's three B x (F K) x H1 contractions + the tail's small ones
     step_bytes = float(ab["fwd"] + ab["bwd_adam"]) * B
     hid = cfg["hidden_units"]
     tail_fl = sum(2.0 * B * a_ * b_ * 3 for a_, b_ in zip(hid[:-1], hid[1:]))
     step_flops = 3 * l1_flops + tail_fl
-    result["roofline_step"] = {
+    out["roofline_step"] = {
         "algorithmic_bytes_per_step": step_bytes, "hbm_GBps": round(step_bytes / (ms * 1e-3) / 1e9, 1),
         "frac_hbm_peak": round(step_bytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
         "flops_per_step": step_flops, "TFLOPs": round(step_flops / (ms * 1e-3) / 1e12, 2),
@@ -456,28 +495,7 @@ def bench_train(args, rank, world, dev):
         "serial_ideal_ms": round(step_bytes / (HBM_PEAK_GBS * 1e9) * 1e3 + step_flops / (MFMA_F32_PEAK_TF * 1e12) * 1e3, 4),
         "note": "the HBM-bound kernels (row update, statistics, segment build) and the MFMA-bound first-layer kernels run "
                 "back to back: the step's floor is the SUM of the two ideals"}
-    if args.steady_seconds > 0 and world == 1:      # >= 1 s of steady-state replays next to the driver's short region
-        n = max(args.steps, int(args.steady_seconds / max(dt / args.steps, 1e-6)) + 1)
-        pool.ensure(n + 6)
-        if graphed:
-            net.enable_graph(True)
-            for s in range(4):
-                one_step()
-        barrier()
-        t1 = time.perf_counter()
-        for s in range(n):
-            loss_ss = one_step()
-        barrier()
-        result["steady_state"] = {"steps": n, "ms_per_step": round((time.perf_counter() - t1) / n * 1e3, 4),
-                                  "final_loss": round(float(loss_ss), 5), "distinct_batches": pool.cursor}
-        result["steady_ms_per_step"] = result["steady_state"]["ms_per_step"]
-        result["steady_steps"] = n
-        # (the driver's record keeps `config`, `roofline` and `cpu_baseline` whole and only the NAMES of other keys)
-        result["config"]["steady_ms_per_step"] = result["steady_ms_per_step"]
-        result["config"]["steady_steps"] = n
-    host = [host_batch(cfg, b) for b in first]
-    del net
-    return result, cfg, host
+    return out
 
 
 DUMP_ROWS = 8192                # embedding rows of the last timed batch sampled into the dump
@@ -859,9 +877,14 @@ def main():
                     help="deepfm = BASELINE cfg 2 (the configuration the metric is quoted on); din / twotower / lightgcn = "
                          "cfg 3 / 4 / 5 at full size on one GPU; deepfm_recommend = recommend_user of a DeepFM over cfg 2's "
                          "full catalogue (SURVEY 8 f2)")
-    ap.add_argument("--steady-seconds", type=float, default=1.0,
-                    help="additionally report ms/step over at least this many seconds of steady-state steps (0 = off)")
-    ap.add_argument("--dense-adam-line", action="store_true", help="(default at N=1; kept for older command lines)")
+    ap.add_argument("--full", action="store_true",
+                    help="DeepFM line: after the headline figure, also measure everything beside it (per-kernel times and "
+                         "rooflines, steady state, recommend leg, f32-chain and dense-Adam variants, CPU baselines, cfg 3 / 4 / 5); "
+                         "the --no-* options below skip parts of it")
+    ap.add_argument("--steady-seconds", type=float, default=None,
+                    help="additionally report ms/step over at least this many seconds of steady-state steps (0 = off; "
+                         "default 1 with --full or --workload, else 0)")
+    ap.add_argument("--dense-adam-line", action="store_true", help="(default with --full at N=1; kept for older command lines)")
     ap.add_argument("--no-dense-adam-line", action="store_true",
                     help="skip the second GPU line that times the step with TF1's dense Adam over every table row (the CPU "
                          "port's optimiser semantics)")
@@ -872,7 +895,7 @@ def main():
                     help="materialised deep_embed + library GEMMs for the first layer (round-1 path)")
     ap.add_argument("--no-recommend", action="store_true")
     ap.add_argument("--no-workloads", action="store_true",
-                    help="skip the cfg 3 / 4 / 5 lines (`workloads` object) that the default single-GPU run appends")
+                    help="skip the cfg 3 / 4 / 5 lines (`workloads` object) that a single-GPU --full run appends")
     ap.add_argument("--force-sharded", action="store_true",
                     help="run the multi-GPU net even at world size 1 (measures the exchange glue)")
     ap.add_argument("--parallel", choices=["row", "field"], default="row",
@@ -888,6 +911,8 @@ def main():
         raise SystemExit("--steps must be at least 1")
     if args.dump_outputs and (args.workload != "deepfm" or args.gpus > 1 or args.force_sharded):
         raise SystemExit("--dump-outputs covers the single-GPU DeepFM training step (--workload deepfm, --gpus 1)")
+    if args.steady_seconds is None:
+        args.steady_seconds = 1.0 if (args.full or args.workload != "deepfm") else 0.0
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -946,6 +971,16 @@ def main():
         _emit(res, rank, stdout_fd)
         return
     result, cfg, host = bench_train(args, rank, world, dev)
+    if args.full:
+        full_legs(args, result, cfg, host, rank, world, dev)
+    if torch.distributed.is_initialized():
+        torch.distributed.destroy_process_group()
+    _emit(result, rank, stdout_fd)
+
+
+def full_legs(args, result, cfg, host, rank, world, dev):
+    """`--full`: the legs measured beside the headline DeepFM step, added to its `result` (rank 0): the recommend leg, the
+    f32-chain and dense-Adam variants of the step, the CPU baselines, cfg 3 / 4 / 5 and their summary in `config.other_legs`."""
     _release(dev)
     if not args.no_recommend:
         # (world > 1: the leg holds collectives — a rank that swallowed its own failure would leave the others blocked in
@@ -971,8 +1006,7 @@ def main():
                 result["recommend"]["cpu_baseline"] = bench_recommend_cpu_baseline()
         if not args.no_workloads and not args.force_sharded:
             # the other BASELINE.json configurations at full size on this one GPU, each with its own `roofline` +
-            # `cpu_baseline` (the same functions `--workload {din,twotower,lightgcn}` prints as stand-alone lines): the
-            # driver runs exactly this default command, so every number DESIGN.md quotes is in the line it records
+            # `cpu_baseline` (the same functions `--workload {din,twotower,lightgcn}` prints as stand-alone lines)
             import bench_workloads
 
             result["workloads"] = {}
@@ -982,9 +1016,6 @@ def main():
                 _release(dev)
     if rank == 0:
         result["config"]["other_legs"] = _legs_summary(result)
-    if torch.distributed.is_initialized():
-        torch.distributed.destroy_process_group()
-    _emit(result, rank, stdout_fd)
 
 
 def _legs_summary(result):

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp
-rocprofv3 --kernel-trace --stats -f csv rocpd -d $OUT -o bench -- python $OLDPWD/bench.py --steps 10 --warmup 3 --no-cpu-baseline "$@" > $OUT/bench_stdout.log 2>&1 || true
+rocprofv3 --kernel-trace --stats -f csv rocpd -d $OUT -o bench -- python $OLDPWD/bench.py --steps 10 --warmup 3 --full --no-cpu-baseline "$@" > $OUT/bench_stdout.log 2>&1 || true
 cd $OLDPWD
 ls -R $OUT | head -30
 F=$(find $OUT -name "*kernel_stats.csv" | head -1)

@@ -11,7 +11,7 @@ export TMPDIR=/tmp
 ROOT=$PWD
 OUT=$ROOT/gpurun_out/${RND}_profiles
 TCC="TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum"
-COMMON="--no-cpu-baseline --steady-seconds 0"
+COMMON="--full --no-cpu-baseline --steady-seconds 0"
 for w in $WL; do
   mkdir -p $OUT/$w/trace $OUT/$w/pmc
   case $w in
