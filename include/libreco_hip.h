@@ -877,6 +877,59 @@ int lr_als_half_sweep_f32(const int64_t* rowptr, const int32_t* col, const float
                           const int32_t* plan, int64_t n_light, int64_t n_medium, int64_t n_heavy, int64_t n_chunks,
                           int32_t* fail, void* ws, size_t ws_bytes, int stage_mask, lr_stream_t stream);
 
+/* ----------------------------------------------------------------------------------
+ * UserCF / ItemCF (csrc/cf_sim.hip, csrc/cf_rank.hip) — replace the similarity engine of the CF models,
+ * `invert_*` / `forward_*` of libreco/utils/_similarities.pyx:17-533 (called by utils/similarities.py:32-203), and the
+ * pure-Python ranking of libreco/bases/cf_base.py:212-250 (compute_pred), :310-355 (rank_recommendations,
+ * get_top_k_sims), algorithms/item_cf.py:70-149 and algorithms/user_cf.py:70-147 (predict, recommend_one).
+ *   lr_cf_sim_tile_cols   columns per LDS tile of the similarity kernel (host-only).
+ *   lr_cf_sim_ws_bytes    workspace of lr_cf_sim_f32 (one work counter; host-only).
+ *   lr_cf_sim_f32         the similarity of X (forward CSR, n_x rows, int64 rowptr, int32 ascending col, f32 val) with Y
+ *                         (its transpose): for every pair the products of the shared y are summed in ascending y with an
+ *                         unfused multiply and add, the count of shared y is kept; sim_type 0 cosine (norm = row norms),
+ *                         1 pearson (val of X and Y already mean-centred per x row, norm = the centred norms), 2 jaccard
+ *                         (cnt = row degrees, val / norm unused).  A pair is kept when count >= min_common (values below
+ *                         1 act as 1) and its value is not 0.  Work items (item_row, item_tile) are (row, column tile)
+ *                         pairs in row order then tile order, run in the order `order` (any permutation of the items);
+ *                         pass 0 writes item_nnz (int64 [n_items]), pass 1 writes the kept columns ascending with their
+ *                         values at item_off (int64 [n_items], the exclusive scan of item_nnz).  No atomics on values:
+ *                         identical bits run to run.
+ *   lr_cf_select_max      keys sorted per round by the selection of the top-k and recommend kernels (host-only).
+ *   lr_cf_topk_f32        for every CSR row the first min(k, len) entries by (value descending, column ascending):
+ *                         out_ids / out_sims [n_rows, k], out_len [n_rows].
+ *   lr_cf_recommend_ws_bytes / lr_cf_recommend_f32   for every user u = users[b]: ItemCF (user_cf 0) adds sim * label over
+ *                         u's items (ui: user x item CSR) in ascending id and each item's top-k list (tk_*, [.., tk_k]) in
+ *                         order; UserCF (user_cf 1) over u's top-k users in order and each one's items in ascending id;
+ *                         f32 products and sequential f32 sums.  The touched items are the candidates; with
+ *                         filter_consumed the items of row b of the consumed CSR (cons_ptr int64 [B + 1]) are removed.
+ *                         out_ids / out_scores [B, n_rec] by (score descending, id ascending), out_len = min(n_rec,
+ *                         out_ncand), out_fallback: 0 ranked, 1 nothing touched, 2 every candidate consumed.  ws:
+ *                         B x n_items f32 scores and flags.
+ *   lr_cf_predict_f32     for every pair q the first k entries of similarity row srow[q] (column order) that appear in
+ *                         the sorted interaction row irow[q] with a positive value: rating (rating != 0) sum(l * s / S) /
+ *                         sum(s / S) clipped to [lower, upper], ranking the mean of s; none[q] = 1 and pred[q] =
+ *                         default_pred when there is none. */
+int lr_cf_sim_tile_cols(void);
+size_t lr_cf_sim_ws_bytes(void);
+int lr_cf_sim_f32(const int64_t* x_ptr, const int32_t* x_col, const float* x_val, const int64_t* y_ptr,
+                  const int32_t* y_col, const float* y_val, int64_t n_x, const float* norm, const int32_t* cnt,
+                  int sim_type, int min_common, const int32_t* item_row, const int32_t* item_tile,
+                  const int32_t* order, int64_t n_items, int pass, int64_t* item_nnz, const int64_t* item_off,
+                  int32_t* out_col, float* out_val, void* ws, size_t ws_bytes, lr_stream_t stream);
+int lr_cf_select_max(void);
+int lr_cf_topk_f32(const int64_t* rowptr, const int32_t* col, const float* val, int64_t n_rows, int64_t k,
+                   int32_t* out_ids, float* out_sims, int32_t* out_len, lr_stream_t stream);
+size_t lr_cf_recommend_ws_bytes(int64_t B, int64_t n_items);
+int lr_cf_recommend_f32(const int32_t* users, int64_t B, int user_cf, const int64_t* ui_ptr, const int32_t* ui_col,
+                        const float* ui_val, const int32_t* tk_ids, const float* tk_sims, const int32_t* tk_len,
+                        int64_t tk_k, int64_t n_items, const int64_t* cons_ptr, const int32_t* cons_idx,
+                        int filter_consumed, int64_t n_rec, int32_t* out_ids, float* out_scores, int32_t* out_len,
+                        int64_t* out_ncand, int32_t* out_fallback, void* ws, size_t ws_bytes, lr_stream_t stream);
+int lr_cf_predict_f32(const int32_t* srow, const int32_t* irow, int64_t n, const int64_t* s_ptr, const int32_t* s_col,
+                      const float* s_val, const int64_t* i_ptr, const int32_t* i_col, const float* i_val, int64_t k,
+                      int rating, float lower, float upper, float default_pred, float* pred, int32_t* none,
+                      lr_stream_t stream);
+
 /* Measurement probe (scripts/mfma_peak.py): iters x 8 back-to-back v_mfma_f32_32x32x2_f32 per wave on
  * 256 x waves_per_simd workgroups — the f32 MFMA rate the chip sustains at the clock it holds under that load. */
 int lr_mfma_f32_probe(int iters, int waves_per_simd, float* out, lr_stream_t stream);

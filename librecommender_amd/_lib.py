@@ -200,6 +200,16 @@ SIGNATURES = {
     "lr_als_gram_f32": (_int, [_p, _i64, _int, _f32, _int, _p, _p, _sz, _p]),
     "lr_als_half_sweep_f32": (_int, [_p, _p, _p, _i64, _p, _p, _int, _p, _int, _int, _int, _p, _i64, _i64, _i64, _i64,
                                      _p, _p, _sz, _int, _p]),
+    "lr_cf_sim_tile_cols": (_int, []),
+    "lr_cf_sim_ws_bytes": (_sz, []),
+    "lr_cf_sim_f32": (_int, [_p, _p, _p, _p, _p, _p, _i64, _p, _p, _int, _int, _p, _p, _p, _i64, _int, _p, _p, _p, _p,
+                             _p, _sz, _p]),
+    "lr_cf_select_max": (_int, []),
+    "lr_cf_topk_f32": (_int, [_p, _p, _p, _i64, _i64, _p, _p, _p, _p]),
+    "lr_cf_recommend_ws_bytes": (_sz, [_i64, _i64]),
+    "lr_cf_recommend_f32": (_int, [_p, _i64, _int, _p, _p, _p, _p, _p, _p, _i64, _i64, _p, _p, _int, _i64, _p, _p, _p,
+                                   _p, _p, _p, _sz, _p]),
+    "lr_cf_predict_f32": (_int, [_p, _p, _i64, _p, _p, _p, _p, _p, _p, _i64, _int, _f32, _f32, _f32, _p, _p, _p]),
 }
 
 _lib = None

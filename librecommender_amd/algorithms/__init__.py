@@ -1,12 +1,14 @@
 from .als import ALS
 from .din import DIN
 from .fm import FM, DeepFM
+from .item_cf import ItemCF
 from .lightgcn import LightGCN
 from .ngcf import NGCF
 from .sim import SIM
 from .transformer import Transformer
 from .two_tower import TwoTower
+from .user_cf import UserCF
 from .youtube_ranking import YouTubeRanking
 from .youtube_retrieval import YouTubeRetrieval
 
-__all__ = ["ALS", "DIN", "DeepFM", "FM", "LightGCN", "NGCF", "SIM", "Transformer", "TwoTower", "YouTubeRanking", "YouTubeRetrieval"]
+__all__ = ["ALS", "DIN", "DeepFM", "FM", "ItemCF", "LightGCN", "NGCF", "SIM", "Transformer", "TwoTower", "UserCF", "YouTubeRanking", "YouTubeRetrieval"]

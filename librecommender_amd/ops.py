@@ -1535,3 +1535,170 @@ def als_half_sweep(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, X
           plan.n_heavy, plan.n_chunks, _ptr(None if use_cg else fail), _ptr(plan.ws), plan.ws.numel(), int(stage_mask),
           _stream())
     return None if use_cg else fail
+
+
+# --------------------------------------------------------------------------------------
+# UserCF / ItemCF (csrc/cf_sim.hip, csrc/cf_rank.hip)
+# --------------------------------------------------------------------------------------
+CF_SIM_TYPES = {"cosine": 0, "pearson": 1, "jaccard": 2}
+CF_SIM_MAX_BYTES = None     # cap on the similarity CSR (columns + values); None: 90 % of the free device memory
+
+
+def cf_sim_tile_cols() -> int:
+    return int(_lib.load().lr_cf_sim_tile_cols())
+
+
+def _cf_sim_cap(device) -> int:
+    if CF_SIM_MAX_BYTES is not None:
+        return int(CF_SIM_MAX_BYTES)
+    free, _ = torch.cuda.mem_get_info(device)
+    return int(free * 0.9)
+
+
+def cf_similarity(x_ptr: torch.Tensor, x_col: torch.Tensor, x_val: torch.Tensor, y_ptr: torch.Tensor,
+                  y_col: torch.Tensor, y_val: torch.Tensor, sim_type: str, min_common: int,
+                  norm: Optional[torch.Tensor] = None, cnt: Optional[torch.Tensor] = None):
+    """The full symmetric similarity CSR (rowptr int64 [n_x + 1], col int32 ascending per row, val f32) of the forward CSR
+    X (n_x rows) against its inverted index Y, in the reference's f32 order (`_similarities.pyx`).  Pearson expects the
+    values of X and Y mean-centred per x row and `norm` the centred norms; jaccard needs `cnt` (int32 row degrees).  The
+    nnz is counted before anything is allocated for the result: a result above the memory cap raises MemoryError."""
+    _req(x_ptr, torch.int64, "x_ptr", 1)
+    _req(x_col, torch.int32, "x_col", 1)
+    _req(y_ptr, torch.int64, "y_ptr", 1)
+    _req(y_col, torch.int32, "y_col", 1)
+    if sim_type not in CF_SIM_TYPES:
+        raise ValueError("sim_type must be one of (`cosine`, `pearson`, `jaccard`)")
+    st = CF_SIM_TYPES[sim_type]
+    jac = st == 2
+    if jac:
+        _req(cnt, torch.int32, "cnt", 1)
+    else:
+        _req(x_val, torch.float32, "x_val", 1)
+        _req(y_val, torch.float32, "y_val", 1)
+        _req(norm, torch.float32, "norm", 1)
+    dev = x_ptr.device
+    n_x = x_ptr.numel() - 1
+    if n_x > 2**31 - 1:
+        raise ValueError("the similarity supports up to 2**31 - 1 rows")
+    T = cf_sim_tile_cols()
+    # work items: (row, tile) over the tiles between the row's smallest and largest co-occurring column
+    nnz = x_col.numel()
+    deg_y = (y_ptr[1:] - y_ptr[:-1])
+    rows_x = torch.repeat_interleave(torch.arange(n_x, device=dev), x_ptr[1:] - x_ptr[:-1], output_size=nnz)
+    yc = x_col.to(torch.int64)
+    work = torch.zeros(n_x, dtype=torch.int64, device=dev).index_add_(0, rows_x, deg_y[yc])
+    first = y_col[y_ptr[:-1].clamp(max=max(y_col.numel() - 1, 0))].to(torch.int64) if y_col.numel() else deg_y
+    last = y_col[(y_ptr[1:] - 1).clamp(min=0)].to(torch.int64) if y_col.numel() else deg_y
+    tmin = torch.full((n_x,), n_x, dtype=torch.int64, device=dev).scatter_reduce_(0, rows_x, first[yc], "amin")
+    tmax = torch.full((n_x,), -1, dtype=torch.int64, device=dev).scatter_reduce_(0, rows_x, last[yc], "amax")
+    tmin, tmax = torch.div(tmin, T, rounding_mode="floor"), torch.div(tmax, T, rounding_mode="floor")
+    span = torch.where(work > 0, tmax - tmin + 1, torch.zeros_like(work))
+    n_items = int(span.sum())
+    rowptr = torch.zeros(n_x + 1, dtype=torch.int64, device=dev)
+    if n_items == 0:
+        return rowptr, torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.float32, device=dev)
+    item_row = torch.repeat_interleave(torch.arange(n_x, device=dev), span, output_size=n_items)
+    istart = torch.cumsum(span, 0) - span
+    item_tile = tmin[item_row] + torch.arange(n_items, device=dev) - istart[item_row]
+    order = torch.argsort(work[item_row], descending=True, stable=True).to(torch.int32)
+    item_row, item_tile = item_row.to(torch.int32).contiguous(), item_tile.to(torch.int32).contiguous()
+    ws = torch.empty(int(_lib.load().lr_cf_sim_ws_bytes()), dtype=torch.uint8, device=dev)
+    item_nnz = torch.zeros(n_items, dtype=torch.int64, device=dev)
+    vals = (None, None, None) if jac else (x_val, y_val, norm)
+    common = (_ptr(x_ptr), _ptr(x_col), _ptr(vals[0]), _ptr(y_ptr), _ptr(y_col), _ptr(vals[1]), n_x, _ptr(vals[2]),
+              _ptr(cnt if jac else None), st, int(min_common), _ptr(item_row), _ptr(item_tile), _ptr(order), n_items)
+    _call("lr_cf_sim_f32", *common, 0, _ptr(item_nnz), 0, 0, 0, _ptr(ws), ws.numel(), _stream())
+    item_end = torch.cumsum(item_nnz, 0)
+    total = int(item_end[-1])
+    need = total * 8 + (n_x + 1) * 8
+    cap = _cf_sim_cap(dev)
+    if need > cap:
+        raise MemoryError(f"the similarity matrix has {total} entries ({need / 2**30:.2f} GiB), above the "
+                          f"{cap / 2**30:.2f} GiB that the device can hold for it; raise `min_common` or use fewer rows")
+    col = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
+    val = torch.empty(max(total, 1), dtype=torch.float32, device=dev)
+    item_off = (item_end - item_nnz).contiguous()
+    _call("lr_cf_sim_f32", *common, 1, 0, _ptr(item_off), _ptr(col), _ptr(val), _ptr(ws), ws.numel(), _stream())
+    rowptr[1:] = torch.cumsum(torch.zeros(n_x, dtype=torch.int64, device=dev).index_add_(0, item_row.to(torch.int64),
+                                                                                          item_nnz), 0)
+    return rowptr, col[:total], val[:total]
+
+
+def cf_topk(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, k: int):
+    """(ids int32 [n, k'], sims f32 [n, k'], len int32 [n]) with k' = min(k, longest row) (at least 1): every row's first
+    min(k, len) entries by (sim descending, column ascending), `cf_base.py:get_top_k_sims`."""
+    _req(rowptr, torch.int64, "rowptr", 1)
+    _req(col, torch.int32, "col", 1)
+    _req(val, torch.float32, "val", 1)
+    if int(k) < 1:
+        raise ValueError("k must be at least 1")
+    n = rowptr.numel() - 1
+    longest = int((rowptr[1:] - rowptr[:-1]).max()) if n > 0 else 0
+    kk = max(1, min(int(k), longest))
+    ids = torch.empty((n, kk), dtype=torch.int32, device=rowptr.device)
+    sims = torch.empty((n, kk), dtype=torch.float32, device=rowptr.device)
+    lens = torch.zeros(n, dtype=torch.int32, device=rowptr.device)
+    _call("lr_cf_topk_f32", _ptr(rowptr), _ptr(col), _ptr(val), n, kk, _ptr(ids), _ptr(sims), _ptr(lens), _stream())
+    return ids, sims, lens
+
+
+CF_RECOMMEND_WS_BYTES = 1 << 30     # per-call scratch of the recommend kernel (scores + flags); batches are cut to fit
+
+
+def cf_recommend(users: torch.Tensor, user_cf: bool, ui_ptr: torch.Tensor, ui_col: torch.Tensor, ui_val: torch.Tensor,
+                 tk_ids: torch.Tensor, tk_sims: torch.Tensor, tk_len: torch.Tensor, n_items: int,
+                 cons_ptr: torch.Tensor, cons_idx: torch.Tensor, filter_consumed: bool, n_rec: int):
+    """ItemCF / UserCF recommendation scores of `users` (int32, inner ids) and the best n_rec candidates by (score
+    descending, id ascending).  cons_ptr / cons_idx: one consumed row per user of `users`.  Returns (ids [B, n_rec],
+    scores [B, n_rec], lens [B], n_candidates [B], fallback [B]: 1 nothing touched, 2 every candidate consumed)."""
+    _req(users, torch.int32, "users", 1)
+    _req(ui_ptr, torch.int64, "ui_ptr", 1)
+    _req(ui_col, torch.int32, "ui_col", 1)
+    _req(ui_val, torch.float32, "ui_val", 1)
+    _req(tk_ids, torch.int32, "tk_ids", 2)
+    _req(tk_sims, torch.float32, "tk_sims", 2)
+    _req(tk_len, torch.int32, "tk_len", 1)
+    _req(cons_ptr, torch.int64, "cons_ptr", 1)
+    _req(cons_idx, torch.int32, "cons_idx", 1)
+    if int(n_rec) < 1:
+        raise ValueError("n_rec must be at least 1")
+    B, dev = users.numel(), users.device
+    if cons_ptr.numel() != B + 1:
+        raise ValueError("cons_ptr must hold one consumed row per user")
+    ids = torch.empty((B, n_rec), dtype=torch.int32, device=dev)
+    scores = torch.empty((B, n_rec), dtype=torch.float32, device=dev)
+    lens = torch.zeros(B, dtype=torch.int32, device=dev)
+    ncand = torch.zeros(B, dtype=torch.int64, device=dev)
+    fallback = torch.zeros(B, dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    per_user = max(1, int(lib.lr_cf_recommend_ws_bytes(1, n_items)) - 256)
+    chunk = max(1, min(B, CF_RECOMMEND_WS_BYTES // per_user))
+    ws = torch.empty(int(lib.lr_cf_recommend_ws_bytes(min(chunk, max(B, 1)), n_items)), dtype=torch.uint8, device=dev)
+    for b0 in range(0, B, chunk):
+        b1 = min(B, b0 + chunk)
+        cp = (cons_ptr[b0:b1 + 1]).contiguous()
+        _call("lr_cf_recommend_f32", _ptr(users[b0:b1]), b1 - b0, 1 if user_cf else 0, _ptr(ui_ptr), _ptr(ui_col),
+              _ptr(ui_val), _ptr(tk_ids), _ptr(tk_sims), _ptr(tk_len), tk_ids.shape[1], int(n_items), _ptr(cp),
+              _ptr(cons_idx), 1 if filter_consumed else 0, int(n_rec), _ptr(ids[b0:b1]), _ptr(scores[b0:b1]),
+              _ptr(lens[b0:b1]), _ptr(ncand[b0:b1]), _ptr(fallback[b0:b1]), _ptr(ws), ws.numel(), _stream())
+    return ids, scores, lens, ncand, fallback
+
+
+def cf_predict(srow: torch.Tensor, irow: torch.Tensor, s_ptr: torch.Tensor, s_col: torch.Tensor, s_val: torch.Tensor,
+               i_ptr: torch.Tensor, i_col: torch.Tensor, i_val: torch.Tensor, k: int, rating: bool, lower: float,
+               upper: float, default_pred: float):
+    """Neighbourhood predictions of the pairs (srow[q], irow[q]) (`cf_base.py:compute_pred`): (pred f32 [n], none int32
+    [n], 1 where no positive neighbour was found and pred is default_pred)."""
+    for t, nm in ((srow, "srow"), (irow, "irow"), (s_col, "s_col"), (i_col, "i_col")):
+        _req(t, torch.int32, nm, 1)
+    for t, nm in ((s_ptr, "s_ptr"), (i_ptr, "i_ptr")):
+        _req(t, torch.int64, nm, 1)
+    _req(s_val, torch.float32, "s_val", 1)
+    _req(i_val, torch.float32, "i_val", 1)
+    n = srow.numel()
+    pred = torch.empty(n, dtype=torch.float32, device=srow.device)
+    none = torch.empty(n, dtype=torch.int32, device=srow.device)
+    _call("lr_cf_predict_f32", _ptr(srow), _ptr(irow), n, _ptr(s_ptr), _ptr(s_col), _ptr(s_val), _ptr(i_ptr),
+          _ptr(i_col), _ptr(i_val), max(0, int(k)), 1 if rating else 0, float(lower), float(upper), float(default_pred),
+          _ptr(pred), _ptr(none), _stream())
+    return pred, none

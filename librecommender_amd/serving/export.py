@@ -102,3 +102,16 @@ def save_online(path: str, model, version: int = 1):
     os.makedirs(export_dir)
     model.save(export_dir, model.model_name.lower(), inference_only=True)
     return export_dir
+
+
+def save_knn(path: str, model, k: int):
+    """Neighbourhood models (`knn.py:16-46`): the common files plus `sim.json`, every row's first k similar ids by
+    (sim descending, id ascending) as `[id, sim]` pairs, from the device top-k of the similarity matrix."""
+    from .. import ops
+
+    _ensure_dir(path)
+    _save_common(path, model)
+    sim = model._device("sim")
+    ids, sims, lens = (t.cpu().numpy() for t in ops.cf_topk(sim.ptr, sim.col, sim.val, k))
+    _dump(path, "sim.json", {str(i): [[int(a), float(b)] for a, b in zip(ids[i, :n].tolist(), sims[i, :n].tolist())]
+                             for i, n in enumerate(lens.tolist())})
