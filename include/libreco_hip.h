@@ -930,6 +930,44 @@ int lr_cf_predict_f32(const int32_t* srow, const int32_t* irow, int64_t n, const
                       int rating, float lower, float upper, float default_pred, float* pred, int32_t* none,
                       lr_stream_t stream);
 
+/* ----------------------------------------------------------------------------------
+ * Swing (csrc/swing.hip) — replaces the score engine of the reference's Swing model, rust/src/graph.rs:143-233
+ * (compute_single_swing: every user pair of every item, the pair's term scattered over the pair's common items, with a
+ * 100 M-entry cache of intersections and a thread pool; compute_swing_scores: the weights 1 / sqrt(|I_u|), :210-213).
+ * The score CSR has the layout of the CF similarity, so lr_cf_topk_f32 / lr_cf_recommend_f32 / lr_cf_predict_f32 rank it.
+ *   lr_swing_tile_cols    columns per LDS tile of the pair-table kernel (host-only).
+ *   lr_swing_lds_users    the longest intersection a wave of the score kernel keeps in LDS (host-only).
+ *   lr_swing_pairs_ws_bytes   workspace of lr_swing_pairs_f32 (one work counter; host-only).
+ *   lr_swing_pairs_f32    the user-pair table: for every u and every v > u that shares an item with u,
+ *                         f_uv = (w_u * w_v) * (1 / (alpha + (c_uv - 1))) with c_uv the number of shared items and
+ *                         w_u = 1 / sqrt(|I_u|), correctly rounded f32 operations, no fused multiply-add
+ *                         (graph.rs:185-186).  u_ptr / u_col: user x item CSR, i_ptr / i_col: its transpose (int64 rowptr,
+ *                         int32 ascending col).  Work items (item_row, item_tile) are (user, column tile) pairs in row then
+ *                         tile order, run in the order `order`; pass 0 writes item_nnz (int64 [n_items]), pass 1 writes
+ *                         the columns ascending and the values at item_off (the exclusive scan of item_nnz).  The counts
+ *                         are accumulated with integer LDS atomics; no floating-point atomics.
+ *   lr_swing_scores_ws_bytes / lr_swing_scores_f32   the scores on a given pattern: s_ptr / s_col is a symmetric item x
+ *                         item CSR pattern (columns ascending, no diagonal) whose entries (i, j) all have at least two
+ *                         common users, s_row the row of every entry, i_ptr / i_col the item x user CSR, max_item_users
+ *                         its longest row, p_* the pair table over n_users users.  One wave per entry with j > i intersects U_i and U_j and
+ *                         sums f_uv over the pairs u < v of the intersection (found in row u by binary search, or by offset when the row holds
+ *                         every v > u; each lane a fixed stride of the pairs, then
+ *                         a fixed butterfly); the sum is written to (i, j) and (j, i): identical bits run to run and
+ *                         s == s^T bit for bit.  ws: a work counter and, when max_item_users exceeds
+ *                         lr_swing_lds_users, one slot of max_item_users int32 per resident wave. */
+int lr_swing_tile_cols(void);
+int lr_swing_lds_users(void);
+size_t lr_swing_pairs_ws_bytes(void);
+int lr_swing_pairs_f32(const int64_t* u_ptr, const int32_t* u_col, const int64_t* i_ptr, const int32_t* i_col,
+                       int64_t n_users, float alpha, const int32_t* item_row, const int32_t* item_tile,
+                       const int32_t* order, int64_t n_items, int pass, int64_t* item_nnz, const int64_t* item_off,
+                       int32_t* out_col, float* out_val, void* ws, size_t ws_bytes, lr_stream_t stream);
+size_t lr_swing_scores_ws_bytes(int64_t max_item_users);
+int lr_swing_scores_f32(const int64_t* i_ptr, const int32_t* i_col, int64_t max_item_users, int64_t n_users,
+                        const int64_t* p_ptr, const int32_t* p_col, const float* p_val, const int64_t* s_ptr,
+                        const int32_t* s_col, const int32_t* s_row, int64_t nnz, float* s_val, void* ws, size_t ws_bytes,
+                        lr_stream_t stream);
+
 /* Measurement probe (scripts/mfma_peak.py): iters x 8 back-to-back v_mfma_f32_32x32x2_f32 per wave on
  * 256 x waves_per_simd workgroups — the f32 MFMA rate the chip sustains at the clock it holds under that load. */
 int lr_mfma_f32_probe(int iters, int waves_per_simd, float* out, lr_stream_t stream);

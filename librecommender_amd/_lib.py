@@ -210,6 +210,12 @@ SIGNATURES = {
     "lr_cf_recommend_f32": (_int, [_p, _i64, _int, _p, _p, _p, _p, _p, _p, _i64, _i64, _p, _p, _int, _i64, _p, _p, _p,
                                    _p, _p, _p, _sz, _p]),
     "lr_cf_predict_f32": (_int, [_p, _p, _i64, _p, _p, _p, _p, _p, _p, _i64, _int, _f32, _f32, _f32, _p, _p, _p]),
+    "lr_swing_tile_cols": (_int, []),
+    "lr_swing_lds_users": (_int, []),
+    "lr_swing_pairs_ws_bytes": (_sz, []),
+    "lr_swing_pairs_f32": (_int, [_p, _p, _p, _p, _i64, _f32, _p, _p, _p, _i64, _int, _p, _p, _p, _p, _p, _sz, _p]),
+    "lr_swing_scores_ws_bytes": (_sz, [_i64]),
+    "lr_swing_scores_f32": (_int, [_p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _sz, _p]),
 }
 
 _lib = None

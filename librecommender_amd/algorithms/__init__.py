@@ -5,10 +5,11 @@ from .item_cf import ItemCF
 from .lightgcn import LightGCN
 from .ngcf import NGCF
 from .sim import SIM
+from .swing import Swing
 from .transformer import Transformer
 from .two_tower import TwoTower
 from .user_cf import UserCF
 from .youtube_ranking import YouTubeRanking
 from .youtube_retrieval import YouTubeRetrieval
 
-__all__ = ["ALS", "DIN", "DeepFM", "FM", "ItemCF", "LightGCN", "NGCF", "SIM", "Transformer", "TwoTower", "UserCF", "YouTubeRanking", "YouTubeRetrieval"]
+__all__ = ["ALS", "DIN", "DeepFM", "FM", "ItemCF", "LightGCN", "NGCF", "SIM", "Swing", "Transformer", "TwoTower", "UserCF", "YouTubeRanking", "YouTubeRetrieval"]

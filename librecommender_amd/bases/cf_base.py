@@ -126,6 +126,8 @@ class _TopkView(Mapping):
 
 
 class CfBase(Base):
+    _warn_all_consumed = True     # UserCF / ItemCF say so when every candidate of a user was consumed; Swing does not
+
     def __init__(self, task, data_info, cf_type, sim_type="cosine", k_sim=20, store_top_k=True, block_size=None,
                  num_threads=1, min_common=1, mode="invert", seed=42, lower_upper_bound=None):
         super().__init__(task, data_info, lower_upper_bound)
@@ -367,8 +369,8 @@ class CfBase(Base):
             if fallback[b] == 1:
                 recs.append(popular_recommendations(self.data_info, inner_id=True, n_rec=n_rec))
             elif fallback[b] == 2:
-                self.print_count += 1
-                if self.print_count < 11:
+                self.print_count += self._warn_all_consumed
+                if self._warn_all_consumed and self.print_count < 11:
                     no_str = f"no suitable recommendation for user {u}, return default recommendation"
                     print(f"{colorize(no_str, 'red')}")
                 recs.append(popular_recommendations(self.data_info, inner_id=True, n_rec=n_rec))

@@ -1557,7 +1557,7 @@ def _cf_sim_cap(device) -> int:
 
 def cf_similarity(x_ptr: torch.Tensor, x_col: torch.Tensor, x_val: torch.Tensor, y_ptr: torch.Tensor,
                   y_col: torch.Tensor, y_val: torch.Tensor, sim_type: str, min_common: int,
-                  norm: Optional[torch.Tensor] = None, cnt: Optional[torch.Tensor] = None):
+                  norm: Optional[torch.Tensor] = None, cnt: Optional[torch.Tensor] = None, cap: Optional[int] = None):
     """The full symmetric similarity CSR (rowptr int64 [n_x + 1], col int32 ascending per row, val f32) of the forward CSR
     X (n_x rows) against its inverted index Y, in the reference's f32 order (`_similarities.pyx`).  Pearson expects the
     values of X and Y mean-centred per x row and `norm` the centred norms; jaccard needs `cnt` (int32 row degrees).  The
@@ -1611,7 +1611,7 @@ def cf_similarity(x_ptr: torch.Tensor, x_col: torch.Tensor, x_val: torch.Tensor,
     item_end = torch.cumsum(item_nnz, 0)
     total = int(item_end[-1])
     need = total * 8 + (n_x + 1) * 8
-    cap = _cf_sim_cap(dev)
+    cap = _cf_sim_cap(dev) if cap is None else int(cap)
     if need > cap:
         raise MemoryError(f"the similarity matrix has {total} entries ({need / 2**30:.2f} GiB), above the "
                           f"{cap / 2**30:.2f} GiB that the device can hold for it; raise `min_common` or use fewer rows")
@@ -1702,3 +1702,172 @@ def cf_predict(srow: torch.Tensor, irow: torch.Tensor, s_ptr: torch.Tensor, s_co
           _ptr(i_col), _ptr(i_val), max(0, int(k)), 1 if rating else 0, float(lower), float(upper), float(default_pred),
           _ptr(pred), _ptr(none), _stream())
     return pred, none
+
+
+# --------------------------------------------------------------------------------------
+# Swing (csrc/swing.hip)
+# --------------------------------------------------------------------------------------
+SWING_MAX_BYTES = None      # cap on the pair table, the score CSR and the kernel's scratch together; None: 90 % of the free memory
+
+
+def _swing_cap(device) -> int:
+    if SWING_MAX_BYTES is not None:
+        return int(SWING_MAX_BYTES)
+    free, _ = torch.cuda.mem_get_info(device)
+    return int(free * 0.9)
+
+
+class _Stages:
+    """HIP-event times of the stages of one call, in ms (scripts/swing_bench.py); inactive without a dict."""
+
+    def __init__(self, out):
+        self.out, self.marks = out, []
+
+    def mark(self, name):
+        if self.out is not None:
+            e = torch.cuda.Event(enable_timing=True)
+            e.record()
+            self.marks.append((name, e))
+
+    def close(self):
+        if self.out is not None:
+            torch.cuda.synchronize()
+            for (_, a), (name, b) in zip(self.marks[:-1], self.marks[1:]):
+                self.out[name] = self.out.get(name, 0.0) + a.elapsed_time(b)
+
+
+def swing_pair_table(u_ptr: torch.Tensor, u_col: torch.Tensor, i_ptr: torch.Tensor, i_col: torch.Tensor, alpha: float,
+                     cap: Optional[int] = None, stages: Optional[dict] = None):
+    """The user-pair table of Swing as an upper user x user CSR (rowptr int64, col int32 ascending, val f32): for every
+    u < v that share an item, w_u * w_v / (alpha + |I_u ^ I_v| - 1) (`graph.rs:185-186`).  u_*: user x item CSR, i_*: its
+    transpose.  Counted before it is allocated: a table above `cap` bytes raises MemoryError."""
+    _req(u_ptr, torch.int64, "u_ptr", 1)
+    _req(u_col, torch.int32, "u_col", 1)
+    _req(i_ptr, torch.int64, "i_ptr", 1)
+    _req(i_col, torch.int32, "i_col", 1)
+    dev = u_ptr.device
+    n_users = u_ptr.numel() - 1
+    if n_users > 2**31 - 1:
+        raise ValueError("Swing supports up to 2**31 - 1 users")
+    st = _Stages(stages)
+    st.mark("start")
+    T = int(_lib.load().lr_swing_tile_cols())
+    nnz = u_col.numel()
+    rowptr = torch.zeros(n_users + 1, dtype=torch.int64, device=dev)
+    empty = (rowptr, torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.float32, device=dev))
+    if nnz == 0:
+        return empty
+    # work items: (user, tile) over the tiles between u + 1 and the largest user that shares an item with u
+    deg_i = i_ptr[1:] - i_ptr[:-1]
+    rows_u = torch.repeat_interleave(torch.arange(n_users, device=dev), u_ptr[1:] - u_ptr[:-1], output_size=nnz)
+    ic = u_col.to(torch.int64)
+    work = torch.zeros(n_users, dtype=torch.int64, device=dev).index_add_(0, rows_u, deg_i[ic])
+    last = i_col[(i_ptr[1:] - 1).clamp(min=0)].to(torch.int64)
+    vmax = torch.full((n_users,), -1, dtype=torch.int64, device=dev).scatter_reduce_(0, rows_u, last[ic], "amax")
+    me = torch.arange(n_users, device=dev)
+    tmin = torch.div(me + 1, T, rounding_mode="floor")
+    tmax = torch.div(vmax, T, rounding_mode="floor")
+    span = torch.where(vmax > me, tmax - tmin + 1, torch.zeros_like(work))
+    n_items = int(span.sum())
+    if n_items == 0:
+        return empty
+    item_row = torch.repeat_interleave(me, span, output_size=n_items)
+    istart = torch.cumsum(span, 0) - span
+    item_tile = tmin[item_row] + torch.arange(n_items, device=dev) - istart[item_row]
+    order = torch.argsort(work[item_row], descending=True, stable=True).to(torch.int32)
+    item_row, item_tile = item_row.to(torch.int32).contiguous(), item_tile.to(torch.int32).contiguous()
+    ws = torch.empty(int(_lib.load().lr_swing_pairs_ws_bytes()), dtype=torch.uint8, device=dev)
+    item_nnz = torch.zeros(n_items, dtype=torch.int64, device=dev)
+    common = (_ptr(u_ptr), _ptr(u_col), _ptr(i_ptr), _ptr(i_col), n_users, float(alpha), _ptr(item_row), _ptr(item_tile),
+              _ptr(order), n_items)
+    st.mark("pairs_plan")
+    _call("lr_swing_pairs_f32", *common, 0, _ptr(item_nnz), 0, 0, 0, _ptr(ws), ws.numel(), _stream())
+    st.mark("pairs_count")
+    item_end = torch.cumsum(item_nnz, 0)
+    total = int(item_end[-1])
+    need = total * 8 + (n_users + 1) * 8
+    cap = _swing_cap(dev) if cap is None else int(cap)
+    if need > cap:
+        raise MemoryError(f"Swing: the user-pair table has {total} entries ({need / 2**30:.2f} GiB), above the "
+                          f"{cap / 2**30:.2f} GiB that the device can hold for it; train on fewer users")
+    col = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
+    val = torch.empty(max(total, 1), dtype=torch.float32, device=dev)
+    item_off = (item_end - item_nnz).contiguous()
+    st.mark("pairs_scan")
+    _call("lr_swing_pairs_f32", *common, 1, 0, _ptr(item_off), _ptr(col), _ptr(val), _ptr(ws), ws.numel(), _stream())
+    rowptr[1:] = torch.cumsum(torch.zeros(n_users, dtype=torch.int64, device=dev).index_add_(
+        0, item_row.to(torch.int64), item_nnz), 0)
+    st.mark("pairs_fill")
+    st.close()
+    return rowptr, col[:total], val[:total]
+
+
+def _csr_add(n: int, a, b):
+    """a + b of two n x n device CSRs with ascending columns; every entry has at most two addends, summed without atomics."""
+    dev = a[0].device
+
+    def keys(ptr, col):
+        rows = torch.repeat_interleave(torch.arange(ptr.numel() - 1, device=dev), ptr[1:] - ptr[:-1],
+                                       output_size=col.numel())
+        return rows * n + col.to(torch.int64)
+
+    ka, kb = keys(a[0], a[1]), keys(b[0], b[1])
+    uniq, inv = torch.unique(torch.cat([ka, kb]), return_inverse=True)
+    val = torch.zeros(uniq.numel(), dtype=torch.float32, device=dev)
+    ia, ib = inv[: ka.numel()], inv[ka.numel():]
+    val[ia] = a[2]
+    val[ib] = val[ib] + b[2]
+    rows = torch.div(uniq, n, rounding_mode="floor")
+    ptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    ptr[1:] = torch.cumsum(torch.bincount(rows, minlength=n), 0)
+    return ptr, (uniq - rows * n).to(torch.int32).contiguous(), val
+
+
+def swing_scores(u_ptr: torch.Tensor, u_col: torch.Tensor, i_ptr: torch.Tensor, i_col: torch.Tensor, alpha: float,
+                 prev=None, stages: Optional[dict] = None):
+    """The Swing score CSR (rowptr int64 [n_items + 1], col int32 ascending per row, val f32; `graph.rs:143-233`) of the
+    user x item pattern u_* with transpose i_*: s[i][j] = sum over the user pairs u < v of U_i ^ U_j of
+    w_u w_v / (alpha + |I_u ^ I_v| - 1).  The pattern (the item pairs with at least two common users) is counted, scanned
+    and filled by the co-occurrence kernel of the CF similarity, the values by csrc/swing.hip; nothing is allocated before
+    its size is known, and a pair table, result or scratch above the memory cap raises MemoryError.  `prev` (rowptr, col,
+    val of an earlier result, at most n_items rows) is added entry by entry: the retrain of `init_item_scores`."""
+    dev = u_ptr.device
+    n_items = i_ptr.numel() - 1
+    cap = _swing_cap(dev)
+    st = _Stages(stages)
+    p_ptr, p_col, p_val = swing_pair_table(u_ptr, u_col, i_ptr, i_col, alpha, cap=cap, stages=stages)
+    used = p_col.numel() * 8 + p_ptr.numel() * 8
+    st.mark("start")
+    cnt = (i_ptr[1:] - i_ptr[:-1]).to(torch.int32)
+    try:
+        s_ptr, s_col, s_val = cf_similarity(i_ptr, i_col, None, u_ptr, u_col, None, "jaccard", 2, cnt=cnt,
+                                            cap=max(cap - used, 0))
+    except MemoryError as e:
+        raise MemoryError(f"Swing: {e}".replace("; raise `min_common` or use fewer rows",
+                                                " next to the user-pair table; train on fewer items")) from e
+    st.mark("pattern")
+    nnz = s_col.numel()
+    if nnz:
+        lib = _lib.load()
+        longest = int(cnt.max())
+        ws_bytes = int(lib.lr_swing_scores_ws_bytes(longest))
+        used += nnz * 12 + s_ptr.numel() * 8
+        if used + ws_bytes > cap:
+            raise MemoryError(f"Swing: the score kernel needs {ws_bytes / 2**30:.2f} GiB of scratch for items with up to "
+                              f"{longest} users, above what is left of the {cap / 2**30:.2f} GiB cap")
+        s_row = torch.repeat_interleave(torch.arange(n_items, device=dev, dtype=torch.int32), s_ptr[1:] - s_ptr[:-1],
+                                        output_size=nnz)
+        s_val = torch.zeros(nnz, dtype=torch.float32, device=dev)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        st.mark("scores_plan")
+        _call("lr_swing_scores_f32", _ptr(i_ptr), _ptr(i_col), longest, u_ptr.numel() - 1, _ptr(p_ptr), _ptr(p_col),
+              _ptr(p_val), _ptr(s_ptr), _ptr(s_col), _ptr(s_row), nnz, _ptr(s_val), _ptr(ws), ws.numel(), _stream())
+        st.mark("scores")
+    out = (s_ptr, s_col, s_val)
+    if prev is not None and prev[1].numel():
+        pp = torch.full((n_items + 1,), int(prev[0][-1]), dtype=torch.int64, device=dev)
+        pp[: prev[0].numel()] = prev[0]
+        out = _csr_add(n_items, (pp, prev[1], prev[2]), out)
+        st.mark("merge_prev")
+    st.close()
+    return out
