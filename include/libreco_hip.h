@@ -968,6 +968,47 @@ int lr_swing_scores_f32(const int64_t* i_ptr, const int32_t* i_col, int64_t max_
                         const int32_t* s_col, const int32_t* s_row, int64_t nnz, float* s_val, void* ws, size_t ws_bytes,
                         lr_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * BPR — replaces the loop of libreco/algorithms/_bpr.pyx:116-399 (SGD / momentum / Adam over (user, positive, negative)
+ * triples) and the forward / backward of the TF graph of libreco/algorithms/bpr.py:161-204.
+ *   lr_bpr_triple_score_f32  per sample s < W:  d = sum_{j < D} U[users[s], j] (I[pos[s], j] - I[neg[s], j])
+ *       (+ ibias[pos[s]] - ibias[neg[s]] if ibias != NULL),  c[s] = 1 / (1 + exp(d)) in [0, 1],  loss[s] (nullable)
+ *       = -log sigmoid(d), finite for every d.  A sample with an id outside its table gets c = -1, loss = 0 and takes no part
+ *       in what follows.  U is [nU, ldu], I is [nI, ldi] (ldu, ldi >= D).  mode:
+ *         LR_BPR_SCORE  nothing else is written;
+ *         LR_BPR_STASH  gu [W, D] = I[pos] - I[neg], the window-start difference the user pass of the engine reads;
+ *         LR_BPR_GRAD   the per-position gradient rows of gscale * sum_s loss[s] (gscale = 1 / B for the mean):
+ *                       gu [W, D] = -a (p - q), gi [2 W, D] = -a u (row 2 s, the positive) and +a u (row 2 s + 1, the
+ *                       negative), gb [2 W] (nullable) = -a, +a, with a = gscale * c[s] — ready for lr_embed_scatter_*.
+ *   lr_bpr_row_update_f32    the ordered row update of one window.  (seg_*, n_seg) is lr_segments_build over the window's
+ *       ids: the W user ids (other_ids == NULL, n == W; `other` is the stash gu [W, D], other_rows = W), or the 2 W item ids
+ *       interleaved positive, negative per sample (other_ids = users [W], n == 2 W; `other` is the user table
+ *       [other_rows, D], not yet updated for this window), so ascending position is ascending sample order.  Every touched
+ *       row takes, once per occurrence and in that order, the reference's step with the gradient
+ *       g = +-c[s] other[.] - reg * row_at_window_start on its columns j < Dw (Dw = D - 1 for users: their bias column is
+ *       never written; Dw = D for items): sgd x += lr g; momentum (0.9) v = 0.9 v + lr g, x += v (state1); adam (0.9,
+ *       0.999, 1e-8, bias correction by `epoch`) m, h in state1, state2.  table / state* are [V, D].  The row and its state
+ *       are read and written once and the chain runs in registers: same bits from run to run, no atomics; the loop is
+ *       bounded by the run length, so no id can make it wait.
+ * D in [1, 256] (lr_bpr_supported), otherwise LR_ESHAPE.
+ * ---------------------------------------------------------------------------------- */
+#define LR_BPR_SCORE 0
+#define LR_BPR_STASH 1
+#define LR_BPR_GRAD 2
+#define LR_BPR_SGD 0
+#define LR_BPR_MOMENTUM 1
+#define LR_BPR_ADAM 2
+int lr_bpr_supported(int D);
+int lr_bpr_triple_score_f32(const float* U, int64_t nU, int ldu, const float* I, int64_t nI, int ldi,
+                            const float* ibias, int D, const int32_t* users, const int32_t* pos,
+                            const int32_t* neg, int64_t W, int mode, float gscale, float* c, float* loss,
+                            float* gu, float* gi, float* gb, lr_stream_t stream);
+int lr_bpr_row_update_f32(int optimizer, float* table, float* state1, float* state2, int64_t V, int D, int Dw,
+                          const int32_t* seg_pos, const int32_t* seg_rows, const int32_t* seg_start,
+                          const int32_t* n_seg, int64_t n, const float* c, int64_t W, const float* other,
+                          int64_t other_rows, const int32_t* other_ids, double lr, double reg, int epoch,
+                          lr_stream_t stream);
+
 /* Measurement probe (scripts/mfma_peak.py): iters x 8 back-to-back v_mfma_f32_32x32x2_f32 per wave on
  * 256 x waves_per_simd workgroups — the f32 MFMA rate the chip sustains at the clock it holds under that load. */
 int lr_mfma_f32_probe(int iters, int waves_per_simd, float* out, lr_stream_t stream);

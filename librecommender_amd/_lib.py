@@ -216,6 +216,11 @@ SIGNATURES = {
     "lr_swing_pairs_f32": (_int, [_p, _p, _p, _p, _i64, _f32, _p, _p, _p, _i64, _int, _p, _p, _p, _p, _p, _sz, _p]),
     "lr_swing_scores_ws_bytes": (_sz, [_i64]),
     "lr_swing_scores_f32": (_int, [_p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _sz, _p]),
+    "lr_bpr_supported": (_int, [_int]),
+    "lr_bpr_triple_score_f32": (_int, [_p, _i64, _int, _p, _i64, _int, _p, _int, _p, _p, _p, _i64, _int, _f32, _p, _p, _p, _p,
+                                       _p, _p]),
+    "lr_bpr_row_update_f32": (_int, [_int, _p, _p, _p, _i64, _int, _int, _p, _p, _p, _p, _i64, _p, _i64, _p, _i64, _p,
+                                     C.c_double, C.c_double, _int, _p]),
 }
 
 _lib = None

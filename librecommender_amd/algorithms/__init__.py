@@ -1,4 +1,5 @@
 from .als import ALS
+from .bpr import BPR
 from .din import DIN
 from .fm import FM, DeepFM
 from .item_cf import ItemCF
@@ -12,4 +13,4 @@ from .user_cf import UserCF
 from .youtube_ranking import YouTubeRanking
 from .youtube_retrieval import YouTubeRetrieval
 
-__all__ = ["ALS", "DIN", "DeepFM", "FM", "ItemCF", "LightGCN", "NGCF", "SIM", "Swing", "Transformer", "TwoTower", "UserCF", "YouTubeRanking", "YouTubeRetrieval"]
+__all__ = ["ALS", "BPR", "DIN", "DeepFM", "FM", "ItemCF", "LightGCN", "NGCF", "SIM", "Swing", "Transformer", "TwoTower", "UserCF", "YouTubeRanking", "YouTubeRetrieval"]

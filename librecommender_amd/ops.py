@@ -1871,3 +1871,84 @@ def swing_scores(u_ptr: torch.Tensor, u_col: torch.Tensor, i_ptr: torch.Tensor, 
         st.mark("merge_prev")
     st.close()
     return out
+
+
+# --------------------------------------------------------------------------------------
+# BPR (csrc/bpr.hip): triple score + ordered row update
+# --------------------------------------------------------------------------------------
+BPR_MODES = {"score": 0, "stash": 1, "grad": 2}
+BPR_OPTIMIZERS = {"sgd": 0, "momentum": 1, "adam": 2}
+
+
+def bpr_supported(embed_size: int, with_bias_column: bool = True) -> bool:
+    """Whether the BPR kernels take rows of `embed_size` (+ 1 with the bias column) floats."""
+    return bool(_lib.load().lr_bpr_supported(int(embed_size) + (1 if with_bias_column else 0)))
+
+
+def bpr_triple_score(U: torch.Tensor, I: torch.Tensor, users: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor,
+                     mode: str = "score", ibias: Optional[torch.Tensor] = None, gscale: float = 1.0, want_loss: bool = True,
+                     out: Optional[dict] = None) -> dict:
+    """`lr_bpr_triple_score_f32` over W samples: {"c" [W], "loss" [W] (-log sigmoid(d)), and by `mode` "gu" [W, D] (stash:
+    p - q; grad: the user gradient rows), "gi" [2 W, D] and "gb" [2 W] (grad: item rows and item bias, positive then negative
+    per sample)}.  `out` may carry preallocated buffers with those keys (at least as long; their leading W rows are written)."""
+    _req(U, torch.float32, "U", 2)
+    _req(I, torch.float32, "I", 2)
+    for t_, n_ in ((users, "users"), (pos, "pos"), (neg, "neg")):
+        _req(t_, torch.int32, n_, 1)
+    W, D = users.numel(), U.shape[1]
+    if I.shape[1] != D or pos.numel() != W or neg.numel() != W:
+        raise ValueError("shape mismatch")
+    if ibias is not None:
+        _req(ibias, torch.float32, "ibias")
+        if ibias.numel() != I.shape[0]:
+            raise ValueError("ibias must hold one value per item")
+    m = BPR_MODES[mode]
+    out = {} if out is None else out
+    dev = U.device
+
+    def buf(key, shape, want=True):
+        if not want:
+            return None
+        t = out.get(key)
+        if t is None:
+            t = out[key] = torch.empty(shape, dtype=torch.float32, device=dev)
+        elif _req(t, torch.float32, key).numel() < int(torch.Size(shape).numel()):
+            raise ValueError(f"out[{key!r}] is too small")
+        return t
+
+    c = buf("c", (W,))
+    loss = buf("loss", (W,), want_loss)
+    gu = buf("gu", (W, D), m != 0)
+    gi = buf("gi", (2 * W, D), m == 2)
+    gb = buf("gb", (2 * W,), m == 2 and ibias is not None)
+    _call("lr_bpr_triple_score_f32", _ptr(U), U.shape[0], D, _ptr(I), I.shape[0], D, _ptr(ibias), D, _ptr(users), _ptr(pos),
+          _ptr(neg), W, m, float(gscale), _ptr(c), _ptr(loss), _ptr(gu), _ptr(gi), _ptr(gb), _stream())
+    return out
+
+
+def bpr_row_update(optimizer: str, table: torch.Tensor, seg: Segments, c: torch.Tensor, other: torch.Tensor, lr: float,
+                   reg: float, epoch: int, state1: Optional[torch.Tensor] = None, state2: Optional[torch.Tensor] = None,
+                   users: Optional[torch.Tensor] = None) -> None:
+    """`lr_bpr_row_update_f32`: the ordered update of one window's touched rows of `table` [V, D].  Item rows: `seg` over the
+    2 W interleaved (positive, negative) ids, `users` [W] and `other` = the user table; user rows: `seg` over the W user ids,
+    `users` None and `other` = the stash [W, D] (the bias column, the last one, is not written).  `c` holds at least W values."""
+    _req(table, torch.float32, "table", 2)
+    _req(c, torch.float32, "c", 1)
+    _req(other, torch.float32, "other", 2)
+    V, D = table.shape
+    item = users is not None
+    W = seg.n // 2 if item else seg.n
+    if item:
+        _req(users, torch.int32, "users", 1)
+        if seg.n != 2 * users.numel():
+            raise ValueError("item segments must cover two ids per sample")
+    if V != seg.V or other.shape[1] != D or c.numel() < W or (not item and other.shape[0] < W):
+        raise ValueError("shape mismatch")
+    opt = BPR_OPTIMIZERS[optimizer]
+    for t_, n_, need in ((state1, "state1", opt >= 1), (state2, "state2", opt == 2)):
+        if need:
+            if _req(t_, torch.float32, n_, 2).shape != table.shape:
+                raise ValueError(f"{n_} must have the table's shape")
+    _call("lr_bpr_row_update_f32", opt, _ptr(table), _ptr(state1) if opt >= 1 else None, _ptr(state2) if opt == 2 else None, V, D,
+          D if item else D - 1, _ptr(seg.pos), _ptr(seg.rows), _ptr(seg.start), _ptr(seg.n_seg), seg.n, _ptr(c), W, _ptr(other),
+          other.shape[0] if item else W, _ptr(users), float(lr), float(reg), int(epoch), _stream())
