@@ -109,6 +109,34 @@ def test_grid_is_sized_from_the_device_not_a_constant(dev):
     assert 1 <= r <= cus and r == cus, (r, cus)         # one workgroup per CU of THIS device (LDS: > 80 KB per workgroup)
 
 
+def _stream_beside_the_default_stream(dev, lib):
+    """A stream whose kernels run BESIDE the default stream's.  The runtime spreads its streams over a few hardware queues (four
+    unless GPU_MAX_HW_QUEUES says otherwise) and every queue is shared: a spinner on a stream that shares the default stream's
+    queue runs BEFORE the tail instead of beside it and takes no CU away from it (measured: every fourth new stream, the
+    default stream's kernel then waits the spinner's whole duration instead of 0.1 ms).  Which stream a test gets depends on
+    how many were made before it in the process, so the choice is measured: a 50 ms one-workgroup spinner on the candidate, a
+    tiny kernel on the default stream, and the candidate is taken if that kernel did not wait for the spinner."""
+    import time
+
+    probe = torch.zeros(64, device=dev)
+    warm = torch.cuda.Stream(device=dev)
+    assert lib.lr_probe_occupy(1, 160 * 1024, 1_000, warm.cuda_stream) == 0      # (code objects loaded before anything is timed)
+    probe.add_(1)
+    torch.cuda.synchronize()
+    for _ in range(8):
+        s = torch.cuda.Stream(device=dev)
+        assert lib.lr_probe_occupy(1, 160 * 1024, 50_000, s.cuda_stream) == 0
+        time.sleep(0.005)
+        t0 = time.perf_counter()
+        probe.add_(1)
+        torch.cuda.current_stream().synchronize()
+        waited = time.perf_counter() - t0
+        torch.cuda.synchronize()
+        if waited < 0.020:
+            return s
+    pytest.fail("no new stream runs beside the default stream: every one of 8 shares its hardware queue")
+
+
 def test_barrier_with_cus_taken_away_is_identical_or_raises(dev):
     """A long-running kernel on a second stream owns half of the CUs (one 160 KB-LDS workgroup each) while the one-launch tail
     starts: only part of its workgroups are resident.  (a) the spinner ends within the poll bound: the late workgroups arrive,
@@ -126,7 +154,7 @@ def test_barrier_with_cus_taken_away_is_identical_or_raises(dev):
     torch.cuda.synchronize()
     ref = (float(ref[0]), ref[1].clone(), ref[2].clone(), ref[3].clone(), net.P.grad.clone())
     ref_tail.check()
-    side = torch.cuda.Stream(device=dev)
+    side = _stream_beside_the_default_stream(dev, lib)
 
     # (a) half the CUs are held for 0.2 s: the barrier waits, then completes
     tail = make()
