@@ -1009,6 +1009,56 @@ int lr_bpr_row_update_f32(int optimizer, float* table, float* state1, float* sta
                           int64_t other_rows, const int32_t* other_ids, double lr, double reg, int epoch,
                           lr_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * SVD / SVD++ — replace the forward / backward of the TF graphs of libreco/algorithms/svd.py:103-144 and
+ * libreco/algorithms/svdpp.py:102-135,196-214 (f32, rows of K floats, K in [1, 512]: lr_svd_supported, otherwise LR_ESHAPE).
+ * No float atomics anywhere: same bits from run to run.  Ids outside a table are dropped, never dereferenced.
+ *   lr_svdpp_pool_f32  out[r, :] = P[row(r), :] + |N|^-1/2 sum_e Y[hist_idx[e], :] over e in hist_ptr[row(r)] ..
+ *       hist_ptr[row(r) + 1], in that order (the `sqrtn` combiner of safe_embedding_lookup_sparse: a repeated item counts
+ *       twice in the sum and in |N|).  P [n_users, K] may be NULL (only the pooled term is written).  `rows` int32 [n_rows]
+ *       lists the users, or is NULL: row(r) = r (n_rows <= n_users).  `n_rows_dev` (nullable, needs `rows`): a device int32
+ *       holding how many leading entries of `rows` are valid (the n_seg of lr_segments_build); the rows beyond are not
+ *       written.  An empty history returns P's row bit for bit (zeros without P).  hist_ptr int64 [n_users + 1], hist_idx
+ *       int32 [nnz]; an entry outside [0, n_items) adds nothing but counts in |N|; a user outside [0, n_users) gives a zero row.
+ *       `scale_out` (nullable) [n_rows] receives |N|^-1/2 (0 for an empty history).  A history of any length is one launch.
+ *   lr_mf_score_f32    per sample s < B:  score = bu[users[s]] + bi[items[s]] + <X[x(s), :], Q[items[s], :]> with x(s) =
+ *       xidx[s] (the sample's slot of a pooled block X [nX, K]) or, xidx == NULL, users[s] (X is the user table);  loss[s]:
+ *         LR_MF_MSE            (score - label)^2
+ *         LR_MF_CROSS_ENTROPY  max(s, 0) - s label + log1p(exp(-|s|))
+ *         LR_MF_FOCAL          w (1 - p_t)^2 bce, w = 0.25 label + 0.75 (1 - label), p_t = label p + (1 - label)(1 - p)
+ *       and g[s] = gscale * d loss[s] / d score (gscale = 1 / B for the mean); all three finite for |score| in the
+ *       thousands.  bu, bi nullable (0).  A sample with an id (user, item or x) outside its table gets score = loss = g = 0.
+ *       mode LR_MF_SCORE writes nothing else; LR_MF_GRAD also gx [B, K] = g Q[item] and gq [B, K] = g X[x].
+ *   lr_svdpp_hist_grad_f32  the gradient of Y.  An entry e < n of the concatenated histories of the batch's distinct users
+ *       is (its Y row, ent_slot[e] = its user's slot); (seg_*, n_seg) is lr_segments_build over the n Y rows.  Every touched
+ *       row takes gsum = sum_e scale[ent_slot[e]] * G[ent_slot[e], :] over its run, in run order (G [n_slots, K]: the
+ *       per-user sums of gx; scale [n_slots]: scale_out of the pool); runs of more than 64 entries are summed in chunks of 64
+ *       whose partials are added in chunk order (needs ws of lr_svdpp_hist_grad_ws_bytes(n, K) bytes, contents arbitrary;
+ *       with ws == NULL such runs are walked by one lane group).  No [n, K] buffer is read or written.  mode:
+ *         LR_SVD_HIST_ADAM  Y, m, v [n_items, K]: one Adam step (hp) of every touched row with gsum;
+ *         LR_SVD_HIST_ROWS  grows [>= n_seg, K] = gsum per run, for lr_adam_dense_f32.
+ * ---------------------------------------------------------------------------------- */
+#define LR_MF_MSE 0
+#define LR_MF_CROSS_ENTROPY 1
+#define LR_MF_FOCAL 2
+#define LR_MF_SCORE 0
+#define LR_MF_GRAD 1
+#define LR_SVD_HIST_ADAM 0
+#define LR_SVD_HIST_ROWS 1
+int lr_svd_supported(int K);
+int lr_svdpp_pool_f32(const float* P, const float* Y, int64_t n_users, int64_t n_items, int K,
+                      const int64_t* hist_ptr, const int32_t* hist_idx, int64_t nnz, const int32_t* rows,
+                      const int32_t* n_rows_dev, int64_t n_rows, float* out, float* scale_out, lr_stream_t stream);
+int lr_mf_score_f32(const float* X, int64_t nX, const int32_t* xidx, const float* Q, int64_t n_items,
+                    const float* bu, int64_t n_users, const float* bi, int K, const int32_t* users,
+                    const int32_t* items, const float* labels, int64_t B, int loss_kind, int mode, float gscale,
+                    float* score, float* loss, float* g, float* gx, float* gq, lr_stream_t stream);
+size_t lr_svdpp_hist_grad_ws_bytes(int64_t n_max, int K);
+int lr_svdpp_hist_grad_f32(int mode, float* Y, float* m, float* v, int64_t n_items, int K, const float* G,
+                           const float* scale, int64_t n_slots, const int32_t* ent_slot, const int32_t* seg_pos,
+                           const int32_t* seg_rows, const int32_t* seg_start, const int32_t* n_seg, int64_t n,
+                           float* grows, lr_adam_hp hp, void* ws, size_t ws_bytes, lr_stream_t stream);
+
 /* Measurement probe (scripts/mfma_peak.py): iters x 8 back-to-back v_mfma_f32_32x32x2_f32 per wave on
  * 256 x waves_per_simd workgroups — the f32 MFMA rate the chip sustains at the clock it holds under that load. */
 int lr_mfma_f32_probe(int iters, int waves_per_simd, float* out, lr_stream_t stream);

@@ -221,6 +221,13 @@ SIGNATURES = {
                                        _p, _p]),
     "lr_bpr_row_update_f32": (_int, [_int, _p, _p, _p, _i64, _int, _int, _p, _p, _p, _p, _i64, _p, _i64, _p, _i64, _p,
                                      C.c_double, C.c_double, _int, _p]),
+    "lr_svd_supported": (_int, [_int]),
+    "lr_svdpp_pool_f32": (_int, [_p, _p, _i64, _i64, _int, _p, _p, _i64, _p, _p, _i64, _p, _p, _p]),
+    "lr_mf_score_f32": (_int, [_p, _i64, _p, _p, _i64, _p, _i64, _p, _int, _p, _p, _p, _i64, _int, _int, _f32, _p, _p, _p,
+                               _p, _p, _p]),
+    "lr_svdpp_hist_grad_ws_bytes": (_sz, [_i64, _int]),
+    "lr_svdpp_hist_grad_f32": (_int, [_int, _p, _p, _p, _i64, _int, _p, _p, _i64, _p, _p, _p, _p, _p, _i64, _p, AdamHP, _p,
+                                      _sz, _p]),
 }
 
 _lib = None

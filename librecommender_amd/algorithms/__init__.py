@@ -6,6 +6,8 @@ from .item_cf import ItemCF
 from .lightgcn import LightGCN
 from .ngcf import NGCF
 from .sim import SIM
+from .svd import SVD
+from .svdpp import SVDpp
 from .swing import Swing
 from .transformer import Transformer
 from .two_tower import TwoTower
@@ -13,4 +15,4 @@ from .user_cf import UserCF
 from .youtube_ranking import YouTubeRanking
 from .youtube_retrieval import YouTubeRetrieval
 
-__all__ = ["ALS", "BPR", "DIN", "DeepFM", "FM", "ItemCF", "LightGCN", "NGCF", "SIM", "Swing", "Transformer", "TwoTower", "UserCF", "YouTubeRanking", "YouTubeRetrieval"]
+__all__ = ["ALS", "BPR", "DIN", "DeepFM", "FM", "ItemCF", "LightGCN", "NGCF", "SIM", "SVD", "SVDpp", "Swing", "Transformer", "TwoTower", "UserCF", "YouTubeRanking", "YouTubeRetrieval"]

@@ -196,6 +196,14 @@ class SegmentBuilder:
                                                 dtype=torch.uint8, device=self.device)
         return ws
 
+    def hist_ws(self, K: int) -> torch.Tensor:
+        """Persistent workspace of `lr_svdpp_hist_grad_f32` for up to `n_max` entries (contents arbitrary between calls)."""
+        ws = self._long_ws.get(("hist", K))
+        if ws is None:
+            ws = self._long_ws[("hist", K)] = torch.empty(max(_lib.load().lr_svdpp_hist_grad_ws_bytes(self.n_max, K), 256),
+                                                          dtype=torch.uint8, device=self.device)
+        return ws
+
     def build(self, idx: torch.Tensor, want_slots: bool = False) -> Segments:
         """``want_slots``: also emit the run number of every position (``seg.slots``)."""
         _req(idx, torch.int32, "idx")
@@ -1952,3 +1960,116 @@ def bpr_row_update(optimizer: str, table: torch.Tensor, seg: Segments, c: torch.
     _call("lr_bpr_row_update_f32", opt, _ptr(table), _ptr(state1) if opt >= 1 else None, _ptr(state2) if opt == 2 else None, V, D,
           D if item else D - 1, _ptr(seg.pos), _ptr(seg.rows), _ptr(seg.start), _ptr(seg.n_seg), seg.n, _ptr(c), W, _ptr(other),
           other.shape[0] if item else W, _ptr(users), float(lr), float(reg), int(epoch), _stream())
+
+
+# --------------------------------------------------------------------------------------
+# SVD / SVD++ (csrc/svd.hip)
+# --------------------------------------------------------------------------------------
+MF_LOSSES = {"mse": 0, "cross_entropy": 1, "focal": 2}
+
+
+def svd_supported(embed_size: int) -> bool:
+    """Whether the SVD / SVD++ kernels take rows of `embed_size` floats."""
+    return bool(_lib.load().lr_svd_supported(int(embed_size)))
+
+
+def svdpp_pool(P: Optional[torch.Tensor], Y: torch.Tensor, hist_ptr: torch.Tensor, hist_idx: torch.Tensor,
+               rows: Optional[torch.Tensor] = None, n_rows_dev: Optional[torch.Tensor] = None, n_rows: Optional[int] = None,
+               n_users: Optional[int] = None, want_scale: bool = False):
+    """`lr_svdpp_pool_f32`: out[r] = P[row(r)] + |N|^-1/2 sum of the Y rows of that user's history (`hist_ptr` int64
+    [n_users + 1], `hist_idx` int32).  `rows` int32 lists the users (`n_rows_dev`: a device int32 count of its valid leading
+    entries, the rows beyond stay unwritten) or is None: every user.  `P` may be None (the pooled term alone).  Returns out
+    [n_rows, K], and with `want_scale` also |N|^-1/2 per row."""
+    _req(Y, torch.float32, "Y", 2)
+    _req(hist_ptr, torch.int64, "hist_ptr", 1)
+    _req(hist_idx, torch.int32, "hist_idx", 1)
+    K = Y.shape[1]
+    nU = hist_ptr.numel() - 1 if n_users is None else int(n_users)
+    if P is not None:
+        if _req(P, torch.float32, "P", 2).shape != (nU, K):
+            raise ValueError("P must be [n_users, K]")
+    if hist_ptr.numel() != nU + 1:
+        raise ValueError("hist_ptr must hold n_users + 1 offsets")
+    if rows is not None:
+        _req(rows, torch.int32, "rows", 1)
+        n = rows.numel() if n_rows is None else int(n_rows)
+        if n > rows.numel():
+            raise ValueError("n_rows exceeds the row list")
+    else:
+        if n_rows_dev is not None:
+            raise ValueError("n_rows_dev needs a row list")
+        n = nU if n_rows is None else int(n_rows)
+    if n_rows_dev is not None:
+        _req(n_rows_dev, torch.int32, "n_rows_dev")
+    out = torch.empty((max(n, 1), K), dtype=torch.float32, device=Y.device)
+    scale = torch.empty(max(n, 1), dtype=torch.float32, device=Y.device) if want_scale else None
+    _call("lr_svdpp_pool_f32", _ptr(P), _ptr(Y), nU, Y.shape[0], K, _ptr(hist_ptr), _ptr(hist_idx), hist_idx.numel(), _ptr(rows),
+          _ptr(n_rows_dev), n, _ptr(out), _ptr(scale), _stream())
+    return (out[:n], scale[:n]) if want_scale else out[:n]
+
+
+def mf_score(X: torch.Tensor, Q: torch.Tensor, bu: Optional[torch.Tensor], bi: Optional[torch.Tensor], users: torch.Tensor,
+             items: torch.Tensor, labels: torch.Tensor, loss: str, xidx: Optional[torch.Tensor] = None, mode: str = "score",
+             gscale: float = 1.0) -> dict:
+    """`lr_mf_score_f32` over B samples: {"score", "loss", "g" [B]} and with mode="grad" also "gx" [B, K] = g Q[item] and
+    "gq" [B, K] = g X[x].  `X` is the user table (x = the user) or, with `xidx`, a block of rows addressed per sample."""
+    _req(X, torch.float32, "X", 2)
+    _req(Q, torch.float32, "Q", 2)
+    for t_, n_ in ((users, "users"), (items, "items")):
+        _req(t_, torch.int32, n_, 1)
+    _req(labels, torch.float32, "labels", 1)
+    B, K = users.numel(), X.shape[1]
+    if Q.shape[1] != K or items.numel() != B or labels.numel() != B:
+        raise ValueError("shape mismatch")
+    nU = X.shape[0]
+    if xidx is not None:
+        if _req(xidx, torch.int32, "xidx", 1).numel() != B:
+            raise ValueError("xidx must hold one row per sample")
+        nU = bu.numel() if bu is not None else (1 << 31) - 1
+    for t_, n_, n in ((bu, "bu", nU), (bi, "bi", Q.shape[0])):
+        if t_ is not None and _req(t_, torch.float32, n_).numel() != n:
+            raise ValueError(f"{n_} must hold one value per row")
+    if mode not in ("score", "grad"):
+        raise ValueError("mode must be `score` or `grad`")
+    dev = X.device
+    out = {k: torch.empty(max(B, 1), dtype=torch.float32, device=dev)[:B] for k in ("score", "loss", "g")}
+    if mode == "grad":
+        out["gx"] = torch.empty((max(B, 1), K), dtype=torch.float32, device=dev)[:B]
+        out["gq"] = torch.empty((max(B, 1), K), dtype=torch.float32, device=dev)[:B]
+    _call("lr_mf_score_f32", _ptr(X), X.shape[0], _ptr(xidx), _ptr(Q), Q.shape[0], _ptr(bu), nU, _ptr(bi), K, _ptr(users),
+          _ptr(items), _ptr(labels), B, MF_LOSSES[loss], 1 if mode == "grad" else 0, float(gscale), _ptr(out["score"]),
+          _ptr(out["loss"]), _ptr(out["g"]), _ptr(out.get("gx")), _ptr(out.get("gq")), _stream())
+    return out
+
+
+def svdpp_hist_grad(G: torch.Tensor, scale: torch.Tensor, ent_slot: torch.Tensor, seg: Segments, Y: Optional[torch.Tensor] = None,
+                    m: Optional[torch.Tensor] = None, v: Optional[torch.Tensor] = None, hp: Optional[AdamHP] = None,
+                    ws: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """`lr_svdpp_hist_grad_f32`: every Y row touched by the entries (`seg` over their Y rows, `ent_slot` their user slots)
+    takes sum_e scale[slot_e] G[slot_e] in run order.  With `Y`, `m`, `v` and `hp`: the fused Adam step on those rows
+    (returns None); without: the sums per run, [min(seg.n, n_items), K] with the first n_seg rows written, for `adam_dense`.
+    No [entries, K] array is allocated in either form."""
+    _req(G, torch.float32, "G", 2)
+    _req(scale, torch.float32, "scale", 1)
+    _req(ent_slot, torch.int32, "ent_slot", 1)
+    K = G.shape[1]
+    if ent_slot.numel() < seg.n or scale.numel() > G.shape[0]:
+        raise ValueError("shape mismatch")
+    fused = Y is not None
+    if fused:
+        for t_, n_ in ((Y, "Y"), (m, "m"), (v, "v")):
+            if _req(t_, torch.float32, n_, 2).shape != (seg.V, K):
+                raise ValueError(f"{n_} must be [n_items, K]")
+        if hp is None:
+            raise ValueError("the fused form needs the Adam hyper-parameters")
+    # one row per touched y row, never per entry: n_seg <= min(entries, n_items)
+    grows = None if fused else torch.empty((max(min(seg.n, seg.V), 1), K), dtype=torch.float32, device=G.device)
+    if ws is None and seg.n > 0:
+        if seg.owner is not None and hasattr(seg.owner, "hist_ws"):
+            ws = seg.owner.hist_ws(K)                 # kept with the builder: no allocation per step
+        else:
+            ws = torch.empty(max(_lib.load().lr_svdpp_hist_grad_ws_bytes(seg.n, K), 256), dtype=torch.uint8, device=G.device)
+    _call("lr_svdpp_hist_grad_f32", 0 if fused else 1, _ptr(Y), _ptr(m), _ptr(v), seg.V, K, _ptr(G), _ptr(scale), scale.numel(),
+          _ptr(ent_slot), _ptr(seg.pos), _ptr(seg.rows), _ptr(seg.start), _ptr(seg.n_seg), seg.n, _ptr(grows),
+          hp if hp is not None else adam_hp(0.0, 1), _ptr(ws), 0 if ws is None else ws.numel(), _stream())
+    return grows
