@@ -20,7 +20,7 @@
 //          The row's interactions are cut into kChunk-interaction chunks, each formed into a K x K (+ K) partial slab by its
 //          own workgroup; a second kernel sums one row's slabs in chunk order onto G0 and solves as the medium path does.
 //          4,096 interactions keep a chunk's slab traffic (17 KB at K = 64) small against its 1 MB of gathered rows.
-#include "common.hpp"
+#include "tile_csr.hpp"   // set_lds
 
 namespace lr {
 namespace {
@@ -452,13 +452,6 @@ __global__ __launch_bounds__(kBlock) void als_heavy_solve_kernel(float* __restri
     if (use_cg) solve_cg(L.sA, L.lda, L.sb, L.sx, L.sp, L.sRed, K, X + m * K, cg_steps);
     else solve_chol(L.sA, L.lda, L.sb, L.sRed, K, X + m * K, fail + m);
   }
-}
-
-template <typename Kern>
-int set_lds(Kern kern, size_t bytes) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     static_cast<int>(bytes));
-  return e == hipSuccess ? LR_OK : static_cast<int>(e);
 }
 
 size_t light_lds_bytes(int K) {

@@ -14,19 +14,12 @@
 // whole wave.  No atomics, no inter-workgroup wait: the chain loop is bounded by the run length read from the segments.
 #include <math.h>
 
-#include "common.hpp"
+#include "row_group.hpp"
 
 namespace lr {
 
 constexpr int kBprMaxD = 256;
 constexpr int kChainBlock = 8;   // occurrences of a row whose operands are fetched together (ordered row update)
-
-template <int G>
-__device__ __forceinline__ float group_sum(float x) {
-#pragma unroll
-  for (int o = G / 2; o > 0; o >>= 1) x += __shfl_xor(x, o);
-  return x;
-}
 
 // ---- triple score ------------------------------------------------------------------------
 template <int G, int R>
@@ -36,7 +29,7 @@ __global__ __launch_bounds__(kBlock) void bpr_score_kernel(
     const int32_t* __restrict__ neg, int64_t W, int mode, float gscale, float* __restrict__ c_out,
     float* __restrict__ loss_out, float* __restrict__ gu, float* __restrict__ gi, float* __restrict__ gb) {
   const int lane = threadIdx.x % G;
-  const int64_t s = (static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x) / G;
+  const int64_t s = group_index<G>();
   const bool in = s < W;
   int32_t u = -1, p = -1, q = -1;
   if (in) {
@@ -162,8 +155,8 @@ __global__ __launch_bounds__(kBlock) void bpr_update_kernel(
   const int lane = threadIdx.x % G;
   int64_t nseg = *n_seg;
   if (nseg > n) nseg = n;
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * (kBlock / G);
-  for (int64_t run = (static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x) / G; run < nseg; run += stride) {
+  const int64_t stride = group_stride<G>();
+  for (int64_t run = group_index<G>(); run < nseg; run += stride) {
     const int64_t row = seg_rows[run];
     int b = seg_start[run], e = seg_start[run + 1];
     if (row < 0 || row >= V || b < 0) continue;
@@ -224,23 +217,13 @@ static int update_launch(hipStream_t st, float* table, float* s1, float* s2, int
   return launch_status();
 }
 
-// group size and dwords per lane for a row of D floats
-#define LR_BPR_DISPATCH(D, CALL)                 \
-  do {                                           \
-    if ((D) <= 16) return CALL(16, 1);           \
-    if ((D) <= 32) return CALL(16, 2);           \
-    if ((D) <= 64) return CALL(32, 2);           \
-    if ((D) <= 128) return CALL(64, 2);          \
-    return CALL(64, 4);                          \
-  } while (0)
-
 template <int OPT>
 static int update_dispatch(hipStream_t st, float* table, float* s1, float* s2, int64_t V, int D, int Dw, const int32_t* seg_pos,
                            const int32_t* seg_rows, const int32_t* seg_start, const int32_t* n_seg, int64_t n, const float* c,
                            int64_t W, const float* other, int64_t other_rows, const int32_t* other_ids, BprCoef k) {
 #define LR_BPR_UPD(G, R) \
   update_launch<OPT, G, R>(st, table, s1, s2, V, D, Dw, seg_pos, seg_rows, seg_start, n_seg, n, c, W, other, other_rows, other_ids, k)
-  LR_BPR_DISPATCH(D, LR_BPR_UPD);
+  LR_ROW_GROUP_DISPATCH_256(D, LR_BPR_UPD);
 #undef LR_BPR_UPD
 }
 
@@ -265,7 +248,7 @@ extern "C" int lr_bpr_triple_score_f32(const float* U, int64_t nU, int ldu, cons
   hipStream_t st = as_stream(stream);
 #define LR_BPR_SCORE_CALL(G, R) \
   score_launch<G, R>(st, U, nU, ldu, I, nI, ldi, ibias, D, users, pos, neg, W, mode, gscale, c, loss, gu, gi, gb)
-  LR_BPR_DISPATCH(D, LR_BPR_SCORE_CALL);
+  LR_ROW_GROUP_DISPATCH_256(D, LR_BPR_SCORE_CALL);
 #undef LR_BPR_SCORE_CALL
 }
 

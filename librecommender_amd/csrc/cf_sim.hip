@@ -8,8 +8,8 @@
 // columns, and a barrier separates consecutive y, so every column is accumulated in ascending y with an unfused multiply
 // and add: the reference's f32 order, with no atomics.  (x1, x2) and (x2, x1) get the same bits because the product is
 // commutative.  The count pass writes the nnz of every work item; the fill pass recomputes and writes the columns in
-// ascending order at the item's offset (an exclusive scan of the counts).
-#include "common.hpp"
+// ascending order at the item's offset (an exclusive scan of the counts): the claim and the emit of tile_csr.hpp.
+#include "tile_csr.hpp"
 
 // The reference rounds every product and every sum to f32 (no contraction into an FMA).  HIP's __fmul_rn / __fadd_rn are
 // plain operators in a header compiled with contraction on, so the two would still fuse; these are not contracted.
@@ -55,15 +55,6 @@ struct SimArgs {
   int* counter;
 };
 
-__device__ __forceinline__ int64_t lower_bound_i32(const int32_t* __restrict__ a, int64_t lo, int64_t hi, int64_t v) {
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (static_cast<int64_t>(a[mid]) < v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
 // The similarity of (x1, x2) from the accumulated product sum and count, 0 when the pair is not kept
 // (_similarities.pyx:125-133 cosine, :232-240 pearson, :330-334 jaccard).
 __device__ __forceinline__ float pair_value(const SimArgs& a, int64_t x1, int64_t x2, float prods, int count) {
@@ -89,14 +80,11 @@ __global__ __launch_bounds__(kSimThreads) void cf_sim_kernel(SimArgs a) {
   int64_t* sWave = reinterpret_cast<int64_t*>(sA + kSimBatch);   // [kSimWaves + 1]
   __shared__ int64_t sItem;
 
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+  const int tid = threadIdx.x;
   const int64_t n_tiles = ceil_div(a.n_x, kSimTile);
 
   for (;;) {
-    if (tid == 0) sItem = atomicAdd(a.counter, 1);
-    __syncthreads();
-    const int64_t slot = sItem;
-    __syncthreads();
+    const int64_t slot = claim_item(a.counter, &sItem);
     if (slot >= a.n_items) break;
     const int64_t item = a.order[slot];
     const int64_t x1 = a.item_row[item];
@@ -164,59 +152,13 @@ __global__ __launch_bounds__(kSimThreads) void cf_sim_kernel(SimArgs a) {
     }
     __syncthreads();
 
-    // Emit: wave w owns the contiguous columns [c0 + w * span, c0 + (w + 1) * span) of the tile, 64 per round; a ballot
-    // keeps the order inside a round, the per-wave totals order the waves.
-    constexpr int span = kSimTile / kSimWaves;
-    const int64_t wb = c0 + static_cast<int64_t>(wave) * span;
-    int64_t kept = 0;
-    for (int r = 0; r < span; r += kWave) {
-      const int64_t c = wb + r + lane;
-      bool keep = false;
-      if (c < c1) {
-        const int idx = static_cast<int>(c - c0);
-        keep = pair_value(a, x1, c, sP[idx], sC[idx]) != 0.0f;
-      }
-      kept += __popcll(__ballot(keep));
-    }
-    if (lane == 0) sWave[wave] = kept;
-    __syncthreads();
-    if (PASS == 0) {
-      if (tid == 0) {
-        int64_t t = 0;
-        for (int w = 0; w < kSimWaves; ++w) t += sWave[w];
-        a.item_nnz[item] = t;
-      }
-    } else {
-      int64_t base = a.item_off[item];
-      for (int w = 0; w < wave; ++w) base += sWave[w];
-      const uint64_t below = (lane == 0) ? 0ull : (~0ull >> (kWave - lane));
-      for (int r = 0; r < span; r += kWave) {
-        const int64_t c = wb + r + lane;
-        bool keep = false;
-        float v = 0.0f;
-        if (c < c1) {
-          const int idx = static_cast<int>(c - c0);
-          v = pair_value(a, x1, c, sP[idx], sC[idx]);
-          keep = v != 0.0f;
-        }
-        const uint64_t m = __ballot(keep);
-        if (keep) {
-          const int64_t pos = base + __popcll(m & below);
-          a.out_col[pos] = static_cast<int32_t>(c);
-          a.out_val[pos] = v;
-        }
-        base += __popcll(m);
-      }
-    }
-    __syncthreads();
+    emit_tile<PASS, kSimThreads, kSimTile>(c0, c1, sWave, a.item_nnz, a.item_off, item, a.out_col, a.out_val,
+                                           [&](int64_t c, int idx, float* v) {
+                                             const float sim = pair_value(a, x1, c, sP[idx], sC[idx]);
+                                             if (v != nullptr) *v = sim;
+                                             return sim != 0.0f;
+                                           });
   }
-}
-
-template <typename Kern>
-int set_lds(Kern kern, size_t bytes) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     static_cast<int>(bytes));
-  return e == hipSuccess ? LR_OK : static_cast<int>(e);
 }
 
 }  // namespace

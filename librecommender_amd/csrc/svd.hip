@@ -17,7 +17,7 @@
 // runs give the same bits.  Ids outside a table are dropped, never dereferenced.
 #include <math.h>
 
-#include "common.hpp"
+#include "row_group.hpp"
 
 namespace lr {
 
@@ -25,13 +25,6 @@ constexpr int kSvdMaxK = 512;
 constexpr int kAhead = 8;          // rows whose gathers are in flight before the first add
 constexpr int kSvdLongRun = 64;    // runs longer than this are summed chunk by chunk
 constexpr int kSvdChunk = 64;
-
-template <int G>
-__device__ __forceinline__ float svd_group_sum(float x) {
-#pragma unroll
-  for (int o = G / 2; o > 0; o >>= 1) x += __shfl_xor(x, o);
-  return x;
-}
 
 // ---- history pool ------------------------------------------------------------------------
 template <int G, int R>
@@ -46,8 +39,8 @@ __global__ __launch_bounds__(kBlock) void svdpp_pool_kernel(
     const int64_t d = *n_rows_dev;
     nr = d < 0 ? 0 : (d < nr ? d : nr);
   }
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * (kBlock / G);
-  for (int64_t r = (static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x) / G; r < nr; r += stride) {
+  const int64_t stride = group_stride<G>();
+  for (int64_t r = group_index<G>(); r < nr; r += stride) {
     const int64_t u = rows != nullptr ? static_cast<int64_t>(rows[r]) : r;
     const bool ok = u >= 0 && u < nU;
     int64_t b = 0, e = 0;
@@ -104,7 +97,7 @@ __global__ __launch_bounds__(kBlock) void mf_score_kernel(
     float* __restrict__ score, float* __restrict__ loss_out, float* __restrict__ g_out, float* __restrict__ gx,
     float* __restrict__ gq) {
   const int lane = threadIdx.x % G;
-  const int64_t s = (static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x) / G;
+  const int64_t s = group_index<G>();
   const bool in = s < B;
   int32_t u = -1, i = -1;
   int64_t xr = -1;
@@ -129,7 +122,7 @@ __global__ __launch_bounds__(kBlock) void mf_score_kernel(
     }
     acc = fmaf(xx[r], qq[r], acc);
   }
-  float sc = svd_group_sum<G>(acc);       // every lane of the wave takes part: no early exit above
+  float sc = group_sum<G>(acc);       // every lane of the wave takes part: no early exit above
   if (ok) sc += (bu != nullptr ? bu[u] : 0.f) + (bi != nullptr ? bi[i] : 0.f);
   float loss, gs;
   if (loss_kind == LR_MF_MSE) {                            // tfops/loss.py:5-8
@@ -284,8 +277,8 @@ __global__ __launch_bounds__(kBlock) void svdpp_hist_kernel(float* __restrict__ 
   const int lane = threadIdx.x % G;
   int64_t n_seg = *h.n_seg;
   if (n_seg > h.n) n_seg = h.n;
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * (kBlock / G);
-  for (int64_t run = (static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x) / G; run < n_seg; run += stride) {
+  const int64_t stride = group_stride<G>();
+  for (int64_t run = group_index<G>(); run < n_seg; run += stride) {
     int p0 = h.seg_start[run], p1 = h.seg_start[run + 1];
     if (p0 < 0) p0 = 0;
     if (p1 > h.n) p1 = static_cast<int>(h.n);
@@ -303,8 +296,8 @@ __global__ __launch_bounds__(kBlock) void svdpp_hist_chunk_kernel(SvdHist h, Svd
   const int lane = threadIdx.x % G;
   int n_chunks = w.counts[1];
   if (n_chunks > w.n_chunk_max) n_chunks = w.n_chunk_max;
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * (kBlock / G);
-  for (int64_t c = (static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x) / G; c < n_chunks; c += stride) {
+  const int64_t stride = group_stride<G>();
+  for (int64_t c = group_index<G>(); c < n_chunks; c += stride) {
     const int slot = w.chunk_slot[c];
     if (slot < 0 || slot >= w.n_long_max) continue;
     const int s = w.long_seg[slot];
@@ -333,8 +326,8 @@ __global__ __launch_bounds__(kBlock) void svdpp_hist_finish_kernel(float* __rest
   const int lane = threadIdx.x % G;
   int n_long = w.counts[0];
   if (n_long > w.n_long_max) n_long = w.n_long_max;
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * (kBlock / G);
-  for (int64_t q0 = (static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x) / G; q0 < n_long; q0 += stride) {
+  const int64_t stride = group_stride<G>();
+  for (int64_t q0 = group_index<G>(); q0 < n_long; q0 += stride) {
     const int s = w.long_seg[q0];
     if (s < 0 || s >= h.n) continue;
     const int64_t base = w.long_base[q0];
@@ -411,22 +404,13 @@ static int hist_launch(hipStream_t st, float* Y, float* m, float* v, int64_t nY,
   return launch_status();
 }
 
-// group size and dwords per lane for a row of K floats
-#define LR_SVD_DISPATCH(K, CALL)                 \
-  do {                                           \
-    if ((K) <= 16) return CALL(16, 1);           \
-    if ((K) <= 32) return CALL(16, 2);           \
-    if ((K) <= 64) return CALL(32, 2);           \
-    if ((K) <= 128) return CALL(64, 2);          \
-    if ((K) <= 256) return CALL(64, 4);          \
-    return CALL(64, 8);                          \
-  } while (0)
-
+// rows of 257 - 512 floats take eight dwords per lane; the narrower ones share BPR's groups
 template <int MODE>
 static int hist_dispatch(hipStream_t st, float* Y, float* m, float* v, int64_t nY, SvdHist h, float* grows, AdamCoef coef,
                          void* ws) {
 #define LR_SVD_HIST(G, R) hist_launch<MODE, G, R>(st, Y, m, v, nY, h, grows, coef, ws)
-  LR_SVD_DISPATCH(h.K, LR_SVD_HIST);
+  if (h.K > 256) return LR_SVD_HIST(64, 8);
+  LR_ROW_GROUP_DISPATCH_256(h.K, LR_SVD_HIST);
 #undef LR_SVD_HIST
 }
 
@@ -448,7 +432,8 @@ extern "C" int lr_svdpp_pool_f32(const float* P, const float* Y, int64_t n_users
   hipStream_t st = as_stream(stream);
 #define LR_SVD_POOL(G, R) \
   pool_launch<G, R>(st, P, Y, n_users, n_items, K, hist_ptr, hist_idx, nnz, rows, n_rows_dev, n_rows, out, scale_out)
-  LR_SVD_DISPATCH(K, LR_SVD_POOL);
+  if (K > 256) return LR_SVD_POOL(64, 8);
+  LR_ROW_GROUP_DISPATCH_256(K, LR_SVD_POOL);
 #undef LR_SVD_POOL
 }
 
@@ -467,7 +452,8 @@ extern "C" int lr_mf_score_f32(const float* X, int64_t nX, const int32_t* xidx, 
 #define LR_SVD_SCORE(G, R)                                                                                              \
   score_launch<G, R>(st, X, nX, xidx, Q, n_items, bu, n_users, bi, K, users, items, labels, B, loss_kind, mode, gscale, \
                      score, loss, g, gx, gq)
-  LR_SVD_DISPATCH(K, LR_SVD_SCORE);
+  if (K > 256) return LR_SVD_SCORE(64, 8);
+  LR_ROW_GROUP_DISPATCH_256(K, LR_SVD_SCORE);
 #undef LR_SVD_SCORE
 }
 

@@ -6,9 +6,10 @@
 //
 // Two stages:
 //   1. swing_pairs_kernel: the user-pair table F, an upper (v > u) user x user CSR with f_uv = w_u * w_v / (alpha + c_uv - 1)
-//      for every pair that shares an item.  Work items are (user u, 8,192-column tile) pairs as in cf_sim.hip; a workgroup
-//      counts c_uv for its tile in LDS with integer atomics (the count does not depend on the order), pass 0 writes the
-//      nnz of every work item, pass 1 recomputes and writes columns ascending and values at the scanned offsets.
+//      for every pair that shares an item.  Work items are (user u, 8,192-column tile) pairs, claimed and emitted by
+//      tile_csr.hpp; a workgroup counts c_uv for its tile in LDS with integer atomics (the count does not depend on the
+//      order), pass 0 writes the nnz of every work item, pass 1 recomputes and writes columns ascending and values at the
+//      scanned offsets.
 //   2. swing_scores_kernel: the score pattern is the set of item pairs with at least two common users (the item x item
 //      co-occurrence of cf_sim.hip with min_common = 2, which counts, scans and fills it).  A wave takes an entry (i, j > i),
 //      intersects U_i with U_j into a sorted list T (LDS, or a global slot when the shorter list exceeds the LDS budget),
@@ -17,7 +18,7 @@
 //      and the 64 partial sums are reduced by a fixed butterfly.  The order depends on |T| alone, so two runs give the same bits; the value is written to (i, j) and to
 //      its mirror (j, i), so the matrix is symmetric bit for bit.
 // Every term is built from correctly rounded f32 sqrt, divisions and unfused products, as the reference builds it.
-#include "common.hpp"
+#include "tile_csr.hpp"
 
 #pragma clang fp contract(off)
 
@@ -34,15 +35,6 @@ constexpr int kScoreChunk = 8;                        // entries claimed per ato
 constexpr int kScoreBlocksPerCU = 5;                  // 32 KB of LDS each
 constexpr int kScoreGrid = kNumCU * kScoreBlocksPerCU;
 constexpr size_t kCounterBytes = 256;
-
-__device__ __forceinline__ int64_t lower_bound_i32(const int32_t* __restrict__ a, int64_t lo, int64_t hi, int64_t v) {
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (static_cast<int64_t>(a[mid]) < v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
 
 // w_u = 1 / sqrt(|I_u|) (graph.rs:210-213)
 __device__ __forceinline__ float user_weight(int64_t deg) { return __fdiv_rn(1.0f, sqrtf(static_cast<float>(deg))); }
@@ -80,10 +72,7 @@ __global__ __launch_bounds__(kPairThreads) void swing_pairs_kernel(PairArgs a) {
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
 
   for (;;) {
-    if (tid == 0) sItem = atomicAdd(a.counter, 1);
-    __syncthreads();
-    const int64_t slot = sItem;
-    __syncthreads();
+    const int64_t slot = claim_item(a.counter, &sItem);
     if (slot >= a.n_items) break;
     const int64_t item = a.order[slot];
     const int64_t u = a.item_row[item];
@@ -105,42 +94,14 @@ __global__ __launch_bounds__(kPairThreads) void swing_pairs_kernel(PairArgs a) {
     }
     __syncthreads();
 
-    // Emit as cf_sim.hip does: wave w owns a contiguous span of the tile, a ballot keeps the order inside a round.
-    constexpr int span = kPairTile / kPairWaves;
-    const int64_t wb = c0 + static_cast<int64_t>(wave) * span;
-    int64_t kept = 0;
-    for (int r = 0; r < span; r += kWave) {
-      const int64_t c = wb + r + lane;
-      const bool keep = c < c1 && sC[static_cast<int>(c - c0)] > 0;
-      kept += __popcll(__ballot(keep));
-    }
-    if (lane == 0) sWave[wave] = kept;
-    __syncthreads();
-    if (PASS == 0) {
-      if (tid == 0) {
-        int64_t t = 0;
-        for (int w = 0; w < kPairWaves; ++w) t += sWave[w];
-        a.item_nnz[item] = t;
-      }
-    } else {
-      int64_t base = a.item_off[item];
-      for (int w = 0; w < wave; ++w) base += sWave[w];
-      const uint64_t below = (lane == 0) ? 0ull : (~0ull >> (kWave - lane));
-      const float wu = user_weight(ue - ub);
-      for (int r = 0; r < span; r += kWave) {
-        const int64_t c = wb + r + lane;
-        const int cnt = c < c1 ? sC[static_cast<int>(c - c0)] : 0;
-        const bool keep = cnt > 0;
-        const uint64_t m = __ballot(keep);
-        if (keep) {
-          const int64_t pos = base + __popcll(m & below);
-          a.out_col[pos] = static_cast<int32_t>(c);
-          a.out_val[pos] = pair_term(wu, user_weight(a.u_ptr[c + 1] - a.u_ptr[c]), a.alpha, cnt);
-        }
-        base += __popcll(m);
-      }
-    }
-    __syncthreads();
+    // The count pass asks only whether the pair shares an item: the term (two square roots, two divisions) is pass 1's.
+    const float wu = PASS == 1 ? user_weight(ue - ub) : 0.0f;
+    emit_tile<PASS, kPairThreads, kPairTile>(
+        c0, c1, sWave, a.item_nnz, a.item_off, item, a.out_col, a.out_val, [&](int64_t c, int idx, float* v) {
+          const int cnt = sC[idx];
+          if (v != nullptr && cnt > 0) *v = pair_term(wu, user_weight(a.u_ptr[c + 1] - a.u_ptr[c]), a.alpha, cnt);
+          return cnt > 0;
+        });
   }
 }
 

@@ -1556,11 +1556,58 @@ def cf_sim_tile_cols() -> int:
     return int(_lib.load().lr_cf_sim_tile_cols())
 
 
-def _cf_sim_cap(device) -> int:
-    if CF_SIM_MAX_BYTES is not None:
-        return int(CF_SIM_MAX_BYTES)
+def _mem_cap(override, device) -> int:
+    """`override` (CF_SIM_MAX_BYTES / SWING_MAX_BYTES as they stand at the call) or 90 % of the free device memory."""
+    if override is not None:
+        return int(override)
     free, _ = torch.cuda.mem_get_info(device)
     return int(free * 0.9)
+
+
+def _tile_work_items(n_rows: int, work: torch.Tensor, tmin: torch.Tensor, span: torch.Tensor):
+    """The (row, tile) work items of csrc/tile_csr.hpp: row r gets the span[r] tiles from tmin[r] on.  Returns (item_row
+    int32, item_tile int32, order int32: the items by the work of their row, heaviest first, n_items); one host read."""
+    dev = span.device
+    n_items = int(span.sum())
+    if n_items == 0:
+        return None, None, None, 0
+    item_row = torch.repeat_interleave(torch.arange(n_rows, device=dev), span, output_size=n_items)
+    istart = torch.cumsum(span, 0) - span
+    item_tile = tmin[item_row] + torch.arange(n_items, device=dev) - istart[item_row]
+    order = torch.argsort(work[item_row], descending=True, stable=True).to(torch.int32)
+    return item_row.to(torch.int32).contiguous(), item_tile.to(torch.int32).contiguous(), order, n_items
+
+
+def _two_pass_csr(fn: str, lead: tuple, rowptr: torch.Tensor, items, ws_bytes: int, cap: Optional[int], max_bytes,
+                  too_large: str, mark=lambda stage: None):
+    """Count, scan, cap check, allocate, fill and rowptr of a two-pass kernel of csrc/tile_csr.hpp: `fn(*lead, item_row,
+    item_tile, order, n_items, pass, item_nnz, item_off, col, val, ws, ws_bytes, stream)`.  Fills `rowptr` (zeros, int64
+    [n_rows + 1]) and returns (rowptr, col, val); col and val are allocated only once the count pass has given their size
+    (one host read), and a result above `cap` bytes (None: `_mem_cap(max_bytes)`, taken after the count pass) raises
+    MemoryError(too_large.format(total=, gib=, cap_gib=))."""
+    item_row, item_tile, order, n_items = items
+    dev = rowptr.device
+    ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=dev)
+    item_nnz = torch.zeros(n_items, dtype=torch.int64, device=dev)
+    common = (*lead, _ptr(item_row), _ptr(item_tile), _ptr(order), n_items)
+    mark("plan")
+    _call(fn, *common, 0, _ptr(item_nnz), 0, 0, 0, _ptr(ws), ws.numel(), _stream())
+    mark("count")
+    item_end = torch.cumsum(item_nnz, 0)
+    total = int(item_end[-1])
+    need = total * 8 + rowptr.numel() * 8
+    cap = _mem_cap(max_bytes, dev) if cap is None else int(cap)
+    if need > cap:
+        raise MemoryError(too_large.format(total=total, gib=need / 2**30, cap_gib=cap / 2**30))
+    col = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
+    val = torch.empty(max(total, 1), dtype=torch.float32, device=dev)
+    item_off = (item_end - item_nnz).contiguous()
+    mark("scan")
+    _call(fn, *common, 1, 0, _ptr(item_off), _ptr(col), _ptr(val), _ptr(ws), ws.numel(), _stream())
+    rowptr[1:] = torch.cumsum(torch.zeros(rowptr.numel() - 1, dtype=torch.int64, device=dev).index_add_(
+        0, item_row.to(torch.int64), item_nnz), 0)
+    mark("fill")
+    return rowptr, col[:total], val[:total]
 
 
 def cf_similarity(x_ptr: torch.Tensor, x_col: torch.Tensor, x_val: torch.Tensor, y_ptr: torch.Tensor,
@@ -1601,35 +1648,16 @@ def cf_similarity(x_ptr: torch.Tensor, x_col: torch.Tensor, x_val: torch.Tensor,
     tmax = torch.full((n_x,), -1, dtype=torch.int64, device=dev).scatter_reduce_(0, rows_x, last[yc], "amax")
     tmin, tmax = torch.div(tmin, T, rounding_mode="floor"), torch.div(tmax, T, rounding_mode="floor")
     span = torch.where(work > 0, tmax - tmin + 1, torch.zeros_like(work))
-    n_items = int(span.sum())
+    items = _tile_work_items(n_x, work, tmin, span)
     rowptr = torch.zeros(n_x + 1, dtype=torch.int64, device=dev)
-    if n_items == 0:
+    if items[3] == 0:
         return rowptr, torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.float32, device=dev)
-    item_row = torch.repeat_interleave(torch.arange(n_x, device=dev), span, output_size=n_items)
-    istart = torch.cumsum(span, 0) - span
-    item_tile = tmin[item_row] + torch.arange(n_items, device=dev) - istart[item_row]
-    order = torch.argsort(work[item_row], descending=True, stable=True).to(torch.int32)
-    item_row, item_tile = item_row.to(torch.int32).contiguous(), item_tile.to(torch.int32).contiguous()
-    ws = torch.empty(int(_lib.load().lr_cf_sim_ws_bytes()), dtype=torch.uint8, device=dev)
-    item_nnz = torch.zeros(n_items, dtype=torch.int64, device=dev)
     vals = (None, None, None) if jac else (x_val, y_val, norm)
-    common = (_ptr(x_ptr), _ptr(x_col), _ptr(vals[0]), _ptr(y_ptr), _ptr(y_col), _ptr(vals[1]), n_x, _ptr(vals[2]),
-              _ptr(cnt if jac else None), st, int(min_common), _ptr(item_row), _ptr(item_tile), _ptr(order), n_items)
-    _call("lr_cf_sim_f32", *common, 0, _ptr(item_nnz), 0, 0, 0, _ptr(ws), ws.numel(), _stream())
-    item_end = torch.cumsum(item_nnz, 0)
-    total = int(item_end[-1])
-    need = total * 8 + (n_x + 1) * 8
-    cap = _cf_sim_cap(dev) if cap is None else int(cap)
-    if need > cap:
-        raise MemoryError(f"the similarity matrix has {total} entries ({need / 2**30:.2f} GiB), above the "
-                          f"{cap / 2**30:.2f} GiB that the device can hold for it; raise `min_common` or use fewer rows")
-    col = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
-    val = torch.empty(max(total, 1), dtype=torch.float32, device=dev)
-    item_off = (item_end - item_nnz).contiguous()
-    _call("lr_cf_sim_f32", *common, 1, 0, _ptr(item_off), _ptr(col), _ptr(val), _ptr(ws), ws.numel(), _stream())
-    rowptr[1:] = torch.cumsum(torch.zeros(n_x, dtype=torch.int64, device=dev).index_add_(0, item_row.to(torch.int64),
-                                                                                          item_nnz), 0)
-    return rowptr, col[:total], val[:total]
+    lead = (_ptr(x_ptr), _ptr(x_col), _ptr(vals[0]), _ptr(y_ptr), _ptr(y_col), _ptr(vals[1]), n_x, _ptr(vals[2]),
+            _ptr(cnt if jac else None), st, int(min_common))
+    return _two_pass_csr("lr_cf_sim_f32", lead, rowptr, items, _lib.load().lr_cf_sim_ws_bytes(), cap, CF_SIM_MAX_BYTES,
+                         "the similarity matrix has {total} entries ({gib:.2f} GiB), above the {cap_gib:.2f} GiB that the "
+                         "device can hold for it; raise `min_common` or use fewer rows")
 
 
 def cf_topk(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, k: int):
@@ -1718,13 +1746,6 @@ def cf_predict(srow: torch.Tensor, irow: torch.Tensor, s_ptr: torch.Tensor, s_co
 SWING_MAX_BYTES = None      # cap on the pair table, the score CSR and the kernel's scratch together; None: 90 % of the free memory
 
 
-def _swing_cap(device) -> int:
-    if SWING_MAX_BYTES is not None:
-        return int(SWING_MAX_BYTES)
-    free, _ = torch.cuda.mem_get_info(device)
-    return int(free * 0.9)
-
-
 class _Stages:
     """HIP-event times of the stages of one call, in ms (scripts/swing_bench.py); inactive without a dict."""
 
@@ -1776,38 +1797,15 @@ def swing_pair_table(u_ptr: torch.Tensor, u_col: torch.Tensor, i_ptr: torch.Tens
     tmin = torch.div(me + 1, T, rounding_mode="floor")
     tmax = torch.div(vmax, T, rounding_mode="floor")
     span = torch.where(vmax > me, tmax - tmin + 1, torch.zeros_like(work))
-    n_items = int(span.sum())
-    if n_items == 0:
+    items = _tile_work_items(n_users, work, tmin, span)
+    if items[3] == 0:
         return empty
-    item_row = torch.repeat_interleave(me, span, output_size=n_items)
-    istart = torch.cumsum(span, 0) - span
-    item_tile = tmin[item_row] + torch.arange(n_items, device=dev) - istart[item_row]
-    order = torch.argsort(work[item_row], descending=True, stable=True).to(torch.int32)
-    item_row, item_tile = item_row.to(torch.int32).contiguous(), item_tile.to(torch.int32).contiguous()
-    ws = torch.empty(int(_lib.load().lr_swing_pairs_ws_bytes()), dtype=torch.uint8, device=dev)
-    item_nnz = torch.zeros(n_items, dtype=torch.int64, device=dev)
-    common = (_ptr(u_ptr), _ptr(u_col), _ptr(i_ptr), _ptr(i_col), n_users, float(alpha), _ptr(item_row), _ptr(item_tile),
-              _ptr(order), n_items)
-    st.mark("pairs_plan")
-    _call("lr_swing_pairs_f32", *common, 0, _ptr(item_nnz), 0, 0, 0, _ptr(ws), ws.numel(), _stream())
-    st.mark("pairs_count")
-    item_end = torch.cumsum(item_nnz, 0)
-    total = int(item_end[-1])
-    need = total * 8 + (n_users + 1) * 8
-    cap = _swing_cap(dev) if cap is None else int(cap)
-    if need > cap:
-        raise MemoryError(f"Swing: the user-pair table has {total} entries ({need / 2**30:.2f} GiB), above the "
-                          f"{cap / 2**30:.2f} GiB that the device can hold for it; train on fewer users")
-    col = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
-    val = torch.empty(max(total, 1), dtype=torch.float32, device=dev)
-    item_off = (item_end - item_nnz).contiguous()
-    st.mark("pairs_scan")
-    _call("lr_swing_pairs_f32", *common, 1, 0, _ptr(item_off), _ptr(col), _ptr(val), _ptr(ws), ws.numel(), _stream())
-    rowptr[1:] = torch.cumsum(torch.zeros(n_users, dtype=torch.int64, device=dev).index_add_(
-        0, item_row.to(torch.int64), item_nnz), 0)
-    st.mark("pairs_fill")
+    lead = (_ptr(u_ptr), _ptr(u_col), _ptr(i_ptr), _ptr(i_col), n_users, float(alpha))
+    out = _two_pass_csr("lr_swing_pairs_f32", lead, rowptr, items, _lib.load().lr_swing_pairs_ws_bytes(), cap, SWING_MAX_BYTES,
+                        "Swing: the user-pair table has {total} entries ({gib:.2f} GiB), above the {cap_gib:.2f} GiB that "
+                        "the device can hold for it; train on fewer users", lambda stage: st.mark("pairs_" + stage))
     st.close()
-    return rowptr, col[:total], val[:total]
+    return out
 
 
 def _csr_add(n: int, a, b):
@@ -1841,7 +1839,7 @@ def swing_scores(u_ptr: torch.Tensor, u_col: torch.Tensor, i_ptr: torch.Tensor, 
     val of an earlier result, at most n_items rows) is added entry by entry: the retrain of `init_item_scores`."""
     dev = u_ptr.device
     n_items = i_ptr.numel() - 1
-    cap = _swing_cap(dev)
+    cap = _mem_cap(SWING_MAX_BYTES, dev)
     st = _Stages(stages)
     p_ptr, p_col, p_val = swing_pair_table(u_ptr, u_col, i_ptr, i_col, alpha, cap=cap, stages=stages)
     used = p_col.numel() * 8 + p_ptr.numel() * 8
