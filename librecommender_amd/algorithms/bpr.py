@@ -31,6 +31,7 @@ from ..bases import EmbedBase
 from ..bases.base import hip_device
 from ..evaluation.evaluate import print_metrics
 from ..layers.embedding import glorot_uniform_
+from ..layers.row_adam import REG_NEEDS_DENSE, NamedTables, RowAdam
 from ..utils.device import to_device
 from ..utils.initializers import truncated_normal
 from ..utils.misc import time_block
@@ -38,42 +39,27 @@ from ..utils.validate import check_fitting, reg_config
 
 OPTIMIZERS = ("sgd", "momentum", "adam")
 N_STATES = {"sgd": 0, "momentum": 1, "adam": 2}
+SAVED = {"user": "embedding/user_embeds_var", "item": "embedding/item_embeds_var", "bias": "embedding/item_bias_var"}
 
 
-class BprNet:
+class BprNet(NamedTables):
     """The variables of `bpr.py:161-204` (`user_embeds_var [n_users, K]`, `item_embeds_var [n_items, K]`,
     `item_bias_var [n_items]`, glorot-uniform) with their Adam moments, and one training step on a batch of triples."""
 
     def __init__(self, n_users, n_items, K, lr, epsilon, reg, norm_embed, dense_adam, seed, device):
         self.n_users, self.n_items, self.K, self.device = int(n_users), int(n_items), int(K), device
-        self.lr, self.epsilon, self.norm_embed, self.dense_adam, self.step = lr, epsilon, norm_embed, dense_adam, 0
+        self.lr, self.epsilon, self.norm_embed = lr, epsilon, norm_embed
         # tf.keras.regularizers.l2(reg) on the variables adds 2 * reg * w to EVERY row's gradient each step
-        # (tfops/configs.py:20-26): representable only with the dense TF1 update (nets/youtube_nets.py:87-92)
-        self.reg = float(reg or 0.0)
-        if self.reg and not dense_adam:
-            raise ValueError("`reg` regularises every embedding row each step (tf.keras.regularizers.l2 on the variables): "
-                             "use `dense_adam=True` with it; the row-wise Adam on touched rows cannot represent that term")
+        # (tfops/configs.py:20-26): representable only with the dense TF1 update (layers/row_adam.py)
+        self.adam = RowAdam(device, dense_adam, reg)
         gen = torch.Generator(device=device)
         gen.manual_seed(seed)
-        self.vars = {}
+        tables = {}
         for name, shape in (("user", (self.n_users, K)), ("item", (self.n_items, K)), ("bias", (self.n_items,))):
             t = torch.empty((shape[0], shape[1] if len(shape) == 2 else 1), dtype=torch.float32, device=device)
             glorot_uniform_(t, shape, gen)
-            self.vars[name] = t
-        self.m = {k: torch.zeros_like(v) for k, v in self.vars.items()}
-        self.v = {k: torch.zeros_like(v) for k, v in self.vars.items()}
-        self._builders, self._slots = {}, {}
-
-    def _segments(self, side, ids):
-        b = self._builders.get(side)
-        if b is None or b.n_max < ids.numel():
-            b = self._builders[side] = ops.SegmentBuilder(ids.numel(), self.vars[side].shape[0], self.device)
-        return b.build(ids)
-
-    def _slot(self, side):
-        if side not in self._slots:
-            self._slots[side] = torch.full((self.vars[side].shape[0],), -1, dtype=torch.int32, device=self.device)
-        return self._slots[side]
+            tables[name] = t
+        super().__init__(tables)
 
     def _grads(self, u, p, q):
         """(mean loss, gu [B, K], gi [2 B, K], gb [2 B]): item rows interleaved positive, negative per sample."""
@@ -100,20 +86,11 @@ class BprNet:
         loss, gu, gi, gb = self._grads(u, p, q)
         with torch.no_grad():
             hp = ops.adam_hp(self.lr, self.step, eps=self.epsilon, tf_style=True)
-            seg_u = self._segments("user", u)
-            seg_i = self._segments("item", torch.stack([p, q], 1).reshape(-1).contiguous())
-            V = self.vars
-            if self.dense_adam:
-                ops.adam_dense(V["user"], self.m["user"], self.v["user"], hp, grows=ops.embed_segment_sum(gu, seg_u), seg=seg_u,
-                               row_slot=self._slot("user"), l2=self.reg)
-                ops.adam_dense(V["item"], self.m["item"], self.v["item"], hp, grows=ops.embed_segment_sum(gi, seg_i), seg=seg_i,
-                               row_slot=self._slot("item"), l2=self.reg)
-                ops.adam_dense(V["bias"], self.m["bias"], self.v["bias"], hp, grows=ops.embed_segment_sum(gb.view(-1, 1), seg_i),
-                               seg=seg_i, row_slot=self._slot("item"), l2=self.reg)
-            else:
-                ops.embed_scatter_adam(V["user"], self.m["user"], self.v["user"], gu, seg_u, hp)
-                ops.embed_scatter_adam_lin(V["item"], self.m["item"], self.v["item"], gi, V["bias"], self.m["bias"],
-                                           self.v["bias"], gb, seg_i, hp)
+            seg_u = self.adam.segments("user", u, self.n_users)
+            seg_i = self.adam.segments("item", torch.stack([p, q], 1).reshape(-1).contiguous(), self.n_items)
+            V, M, S = self.vars, self.m, self.v
+            self.adam.update(hp, seg_u, V["user"], M["user"], S["user"], gu)
+            self.adam.update(hp, seg_i, V["item"], M["item"], S["item"], gi, lin=(V["bias"], M["bias"], S["bias"], gb))
         return loss
 
 
@@ -137,8 +114,7 @@ class BPR(EmbedBase):
         self.use_tf, self.seed, self.optimizer, self.num_threads = use_tf, seed, optimizer, num_threads
         self._device_arg, self.dense_adam = device, dense_adam
         if use_tf and self.reg and not dense_adam:
-            raise ValueError("`reg` regularises every embedding row each step (tf.keras.regularizers.l2 on the variables): "
-                             "use `dense_adam=True` with it; the row-wise Adam on touched rows cannot represent that term")
+            raise ValueError(REG_NEEDS_DENSE)
         self.net = None
         self._U = self._I = None            # engine tables [n, K + 1]
         self._state = None                  # engine optimiser state {"u": [...], "i": [...]}, allocated in `fit`
@@ -274,17 +250,12 @@ class BPR(EmbedBase):
     # ---- persistence ----------------------------------------------------------------------------
     def variables_np(self):
         if self.use_tf:
-            return {f"embedding/{k}": v.cpu().numpy() for k, v in
-                    (("user_embeds_var", self.net.vars["user"]), ("item_embeds_var", self.net.vars["item"]),
-                     ("item_bias_var", self.net.vars["bias"].view(-1)))}
+            return {SAVED[k]: (v.view(-1) if k == "bias" else v).cpu().numpy() for k, v in self.net.vars.items()}
         return {"engine/user_table": self._U.cpu().numpy(), "engine/item_table": self._I.cpu().numpy()}
 
     def optimizer_arrays(self):
         if self.use_tf:
-            out = {"opt::step": np.asarray(self.net.step, dtype=np.int64)}
-            for k in ("user", "item", "bias"):
-                out[f"opt::m_{k}"], out[f"opt::v_{k}"] = self.net.m[k].cpu().numpy(), self.net.v[k].cpu().numpy()
-            return out
+            return self.net.optimizer_arrays()
         out = {"opt::epochs": np.asarray(self._epochs_done, dtype=np.int64)}
         for side in "ui":
             for n, s in enumerate((self._state or {}).get(side, [])):
@@ -294,9 +265,9 @@ class BPR(EmbedBase):
     def load_variables_np(self, arrays):
         with torch.no_grad():
             if self.use_tf:
-                for k, name in (("user", "user_embeds_var"), ("item", "item_embeds_var"), ("bias", "item_bias_var")):
-                    if f"embedding/{name}" in arrays:
-                        self.net.vars[k].copy_(torch.from_numpy(arrays[f"embedding/{name}"]).view_as(self.net.vars[k]))
+                for k, name in SAVED.items():
+                    if name in arrays:
+                        self.net.vars[k].copy_(torch.from_numpy(arrays[name]).view_as(self.net.vars[k]))
             else:
                 if "engine/user_table" in arrays:
                     self._U.copy_(torch.from_numpy(arrays["engine/user_table"]))
@@ -305,33 +276,18 @@ class BPR(EmbedBase):
     def rebuild_model(self, path, model_name, full_assign=True):
         """Retraining on merged data: a freshly built, larger model takes over the saved rows (ids keep their place, new ones
         are appended) and, with `full_assign`, their optimiser state; new ids keep fresh draws and zero state."""
-        old = self.data_info.old_info
-        if old is None:
-            raise ValueError("`rebuild_model` needs a `data_info` produced by `merge_trainset`")
-        self.build_model()
-        self.model_built = True
-        arrays = self._saved_arrays(path, model_name)
-        dev, nu, ni = self.device, int(old.n_users), int(old.n_items)
-
-        def put(dst, key, n):
-            if key in arrays:
-                dst[:n] = torch.from_numpy(arrays[key][:n]).to(dev).view(n, -1)
-
-        with torch.no_grad():
-            if self.use_tf:
-                for k, name, n in (("user", "user_embeds_var", nu), ("item", "item_embeds_var", ni), ("bias", "item_bias_var", ni)):
-                    put(self.net.vars[k], f"embedding/{name}", n)
-                    if full_assign:
-                        put(self.net.m[k], f"opt::m_{k}", n)
-                        put(self.net.v[k], f"opt::v_{k}", n)
-                if full_assign and "opt::step" in arrays:
-                    self.net.step = int(arrays["opt::step"])
-            else:
-                put(self._U, "engine/user_table", nu)
-                put(self._I, "engine/item_table", ni)
-                if full_assign and all(f"opt::{s}{n}" in arrays for s in "ui" for n in range(N_STATES[self.optimizer])):
-                    st = self._new_state()
-                    for side, n_old in (("u", nu), ("i", ni)):
-                        for n, s in enumerate(st[side]):
-                            put(s, f"opt::{side}{n}", n_old)
-                    self._restored_state = st
+        arrays, old = self._begin_rebuild(path, model_name)
+        nu, ni = int(old.n_users), int(old.n_items)
+        if self.use_tf:
+            self.net.take_over(arrays, SAVED.get, lambda k: nu if k == "user" else ni, full_assign)
+            return
+        # the engine's tables and optimiser states under their saved names; the states have no moments of their own
+        tables, n_old = {"engine/user_table": self._U, "engine/item_table": self._I}, {"engine/user_table": nu, "engine/item_table": ni}
+        if full_assign and all(f"opt::{s}{n}" in arrays for s in "ui" for n in range(N_STATES[self.optimizer])):
+            self._restored_state = self._new_state()
+            for side, n_side in (("u", nu), ("i", ni)):
+                for n, s in enumerate(self._restored_state[side]):
+                    tables[f"opt::{side}{n}"], n_old[f"opt::{side}{n}"] = s, n_side
+        # `full_assign` above decides whether the states are among `tables`; `take_over`'s own flag only concerns the m / v
+        # moments and the step count, which this holder does not have
+        NamedTables(tables, m={}, v={}).take_over(arrays, lambda k: k, n_old.get, False)

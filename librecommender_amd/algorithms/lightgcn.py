@@ -116,12 +116,7 @@ class LightGCN(EmbedBase):
     def rebuild_model(self, path, model_name):
         """`torchops/rebuild.py:13-105`: saved user / item embedding rows and their Adam states are
         copied into the (larger) new tables; new ids keep the fresh initialisation / zero moments."""
-        old = self.data_info.old_info
-        if old is None:
-            raise ValueError("`rebuild_model` needs a `data_info` produced by `merge_trainset`")
-        self.build_model()
-        self.model_built = True
-        arrays = self._saved_arrays(path, model_name)
+        arrays, old = self._begin_rebuild(path, model_name)
         n = self.net
         src = np.concatenate([np.arange(old.n_users), old.n_users + np.arange(old.n_items)])
         dst = np.concatenate([np.arange(old.n_users), self.n_users + np.arange(old.n_items)])

@@ -54,12 +54,7 @@ class NGCF(LightGCN):
     def rebuild_model(self, path, model_name):
         """`torchops/rebuild.py:13-105`: node-table rows (and their Adam states) of known users / items
         move to their new positions, the layer weights and their states are taken over whole."""
-        old = self.data_info.old_info
-        if old is None:
-            raise ValueError("`rebuild_model` needs a `data_info` produced by `merge_trainset`")
-        self.build_model()
-        self.model_built = True
-        arrays = self._saved_arrays(path, model_name)
+        arrays, old = self._begin_rebuild(path, model_name)
         n = self.net
         src = np.concatenate([np.arange(old.n_users), old.n_users + np.arange(old.n_items)])
         dst = torch.from_numpy(np.concatenate([np.arange(old.n_users), self.n_users + np.arange(old.n_items)])).to(self.device)

@@ -23,12 +23,11 @@ from .. import ops
 from ..bases import EmbedBase
 from ..bases.base import hip_device
 from ..layers.embedding import glorot_uniform_
+from ..layers.row_adam import REG_NEEDS_DENSE, NamedTables, RowAdam
 from ..utils.device import to_device
 from ..utils.validate import reg_config
 
 VAR_KEYS = ("bu", "pu", "bi", "qi", "yj")
-REG_NEEDS_DENSE = ("`reg` regularises every embedding row each step (tf.keras.regularizers.l2 on the variables): "
-                   "use `dense_adam=True` with it; the row-wise Adam on touched rows cannot represent that term")
 
 
 def max_embed_size():
@@ -68,33 +67,29 @@ def history_csr(user_consumed, n_users, recent_num):
     return ptr, np.ascontiguousarray(idx, dtype=np.int32)
 
 
-class SvdNet:
+class SvdNet(NamedTables):
     """The variables of `svd.py:109-136` / `svdpp.py:108-131,198-213` (`bu [n_users]`, `bi [n_items]` zero; `pu`, `qi` and
     for SVD++ `yj [n_items, K]` glorot-uniform) with their Adam moments, and one training step on a pointwise batch."""
 
     def __init__(self, n_users, n_items, K, lr, epsilon, reg, norm_embed, dense_adam, seed, device, loss, with_history=False):
         self.n_users, self.n_items, self.K, self.device = int(n_users), int(n_items), int(K), device
-        self.lr, self.epsilon, self.norm_embed, self.dense_adam, self.step = lr, epsilon, norm_embed, dense_adam, 0
+        self.lr, self.epsilon, self.norm_embed = lr, epsilon, norm_embed
         self.loss, self.with_history = loss, with_history
         # tf.keras.regularizers.l2(reg) on the variables adds 2 * reg * w to EVERY row's gradient each step
-        # (tfops/configs.py:20-26): representable only with the dense TF1 update
-        self.reg = float(reg or 0.0)
-        if self.reg and not dense_adam:
-            raise ValueError(REG_NEEDS_DENSE)
+        # (tfops/configs.py:20-26): representable only with the dense TF1 update (layers/row_adam.py)
+        self.adam = RowAdam(device, dense_adam, reg)
         gen = torch.Generator(device=device)
         gen.manual_seed(seed)
-        self.vars = {}
+        tables = {}
         for name in VAR_KEYS if with_history else VAR_KEYS[:4]:
             n = self.n_users if name in ("bu", "pu") else self.n_items
             if name in ("bu", "bi"):                                        # tf.zeros_initializer
-                self.vars[name] = torch.zeros((n, 1), dtype=torch.float32, device=device)
+                tables[name] = torch.zeros((n, 1), dtype=torch.float32, device=device)
             else:
                 t = torch.empty((n, self.K), dtype=torch.float32, device=device)
                 glorot_uniform_(t, (n, self.K), gen)
-                self.vars[name] = t
-        self.m = {k: torch.zeros_like(v) for k, v in self.vars.items()}
-        self.v = {k: torch.zeros_like(v) for k, v in self.vars.items()}
-        self._builders, self._slots = {}, {}
+                tables[name] = t
+        super().__init__(tables)
         self.hist_ptr = self.hist_idx = None
 
     # ---- the histories of SVD++ -----------------------------------------------------------------
@@ -107,17 +102,6 @@ class SvdNet:
     def pooled_all(self):
         """z over all users (`svdpp.py:196-214`), the export."""
         return ops.svdpp_pool(self.vars["pu"], self.vars["yj"], self.hist_ptr, self.hist_idx)
-
-    def _segments(self, side, ids, n_rows, want_slots=False):
-        b = self._builders.get(side)
-        if b is None or b.n_max < ids.numel():
-            b = self._builders[side] = ops.SegmentBuilder(max(ids.numel(), 1), n_rows, self.device)
-        return b.build(ids, want_slots=want_slots)
-
-    def _slot(self, key):
-        if key not in self._slots:
-            self._slots[key] = torch.full((self.vars[key].shape[0],), -1, dtype=torch.int32, device=self.device)
-        return self._slots[key]
 
     def _entries(self, seg_u, n):
         """The concatenated history entries of the batch's distinct users: (y row, user slot) per entry.  Index plumbing on
@@ -162,7 +146,7 @@ class SvdNet:
         B = u.numel()
         V, M, S = self.vars, self.m, self.v
         with torch.no_grad():
-            seg_u = self._segments("user", u, self.n_users, want_slots=self.with_history)
+            seg_u = self.adam.segments("user", u, self.n_users, self.with_history)      # (with the positions' run numbers)
         gbi = None
         if self.with_history:
             with torch.no_grad():
@@ -185,22 +169,18 @@ class SvdNet:
                 ent_idx, ent_slot = self._entries(seg_u, B)
                 if ent_idx is not None:
                     G = ops.embed_segment_sum(gx, seg_u)
-                    seg_y = self._segments("hist", ent_idx, self.n_items)
-                    if self.dense_adam:
+                    seg_y = self.adam.segments("hist", ent_idx, self.n_items)
+                    if self.adam.dense:     # the per-row sums come from the history kernel, not from `embed_segment_sum`
                         grows = ops.svdpp_hist_grad(G, scale, ent_slot, seg_y)
-                        ops.adam_dense(V["yj"], M["yj"], S["yj"], hp, grows=grows, seg=seg_y, row_slot=self._slot("yj"), l2=self.reg)
+                        ops.adam_dense(V["yj"], M["yj"], S["yj"], hp, grows=grows, seg=seg_y, row_slot=self.adam.row_slot(V["yj"]),
+                                       l2=self.adam.l2)
                     else:
                         ops.svdpp_hist_grad(G, scale, ent_slot, seg_y, Y=V["yj"], m=M["yj"], v=S["yj"], hp=hp)
-                elif self.dense_adam:
-                    ops.adam_dense(V["yj"], M["yj"], S["yj"], hp, l2=self.reg)
-            seg_i = self._segments("item", i, self.n_items)
-            if self.dense_adam:
-                for key, seg, grad in (("pu", seg_u, gx), ("bu", seg_u, gbu.view(-1, 1)), ("qi", seg_i, gq), ("bi", seg_i, gbi.view(-1, 1))):
-                    ops.adam_dense(V[key], M[key], S[key], hp, grows=ops.embed_segment_sum(grad.contiguous(), seg), seg=seg,
-                                   row_slot=self._slot(key), l2=self.reg)
-            else:
-                ops.embed_scatter_adam_lin(V["pu"], M["pu"], S["pu"], gx, V["bu"], M["bu"], S["bu"], gbu, seg_u, hp)
-                ops.embed_scatter_adam_lin(V["qi"], M["qi"], S["qi"], gq, V["bi"], M["bi"], S["bi"], gbi, seg_i, hp)
+                elif self.adam.dense:
+                    self.adam.update_all_rows(hp, V["yj"], M["yj"], S["yj"])
+            seg_i = self.adam.segments("item", i, self.n_items)
+            self.adam.update(hp, seg_u, V["pu"], M["pu"], S["pu"], gx, lin=(V["bu"], M["bu"], S["bu"], gbu))
+            self.adam.update(hp, seg_i, V["qi"], M["qi"], S["qi"], gq, lin=(V["bi"], M["bi"], S["bi"], gbi))
         return loss
 
 
@@ -249,10 +229,7 @@ class SvdBase(EmbedBase):
         return {f"embedding/{k}_var": (v.view(-1) if k in ("bu", "bi") else v).cpu().numpy() for k, v in self.net.vars.items()}
 
     def optimizer_arrays(self):
-        out = {"opt::step": np.asarray(self.net.step, dtype=np.int64)}
-        for k in self.net.vars:
-            out[f"opt::m_{k}"], out[f"opt::v_{k}"] = self.net.m[k].cpu().numpy(), self.net.v[k].cpu().numpy()
-        return out
+        return self.net.optimizer_arrays()
 
     def load_variables_np(self, arrays):
         with torch.no_grad():
@@ -263,27 +240,9 @@ class SvdBase(EmbedBase):
     def _rebuild(self, path, model_name, full_assign):
         """Retraining on merged data: a freshly built, larger model takes over the saved rows (ids keep their place, new ones
         are appended) and, with `full_assign`, their optimiser state; new ids keep fresh draws and zero state."""
-        old = self.data_info.old_info
-        if old is None:
-            raise ValueError("`rebuild_model` needs a `data_info` produced by `merge_trainset`")
-        self.build_model()
-        self.model_built = True
-        arrays = self._saved_arrays(path, model_name)
-        dev, nu, ni = self.device, int(old.n_users), int(old.n_items)
-
-        def put(dst, key, n):
-            if key in arrays:
-                dst[:n] = torch.from_numpy(arrays[key][:n]).to(dev).view(n, -1)
-
-        with torch.no_grad():
-            for k in self.net.vars:
-                n = nu if k in ("bu", "pu") else ni
-                put(self.net.vars[k], f"embedding/{k}_var", n)
-                if full_assign:
-                    put(self.net.m[k], f"opt::m_{k}", n)
-                    put(self.net.v[k], f"opt::v_{k}", n)
-            if full_assign and "opt::step" in arrays:
-                self.net.step = int(arrays["opt::step"])
+        arrays, old = self._begin_rebuild(path, model_name)
+        self.net.take_over(arrays, lambda k: f"embedding/{k}_var",
+                           lambda k: int(old.n_users if k in ("bu", "pu") else old.n_items), full_assign)
 
 
 class SVD(SvdBase):

@@ -368,12 +368,7 @@ class TwoTower(EmbedBase):
         """`tfops/rebuild.py:12-139` for the two-tower variables (`item_embeds_var` has no OOV row,
         two_tower.py:266-271)."""
         from ..training.rebuild import sparse_growth_index
-        old = self.data_info.old_info
-        if old is None:
-            raise ValueError("`rebuild_model` needs a `data_info` produced by `merge_trainset`")
-        self.build_model()
-        self.model_built = True
-        arrays = self._saved_arrays(path, model_name)
+        arrays, old = self._begin_rebuild(path, model_name)
         t, P, dev = self.net.tables, self.net.P, self.device
         with torch.no_grad():
             for kind, n_old in (("user", old.n_users), ("item", old.n_items), ("sparse", None)):

@@ -166,12 +166,7 @@ class YouTubeRetrieval(EmbedBase):
         restored."""
         from ..training.rebuild import sparse_growth_index
 
-        old = self.data_info.old_info
-        if old is None:
-            raise ValueError("`rebuild_model` needs a `data_info` produced by `merge_trainset`")
-        self.build_model()
-        self.model_built = True
-        arrays = self._saved_arrays(path, model_name)
+        arrays, old = self._begin_rebuild(path, model_name)
         t, P, dev = self.net.tables, self.net.P, self.device
         n_old = int(old.n_items)
         off_old = {"seq_embeds_var": 0, "item_embeds_var": n_old + 1, "sparse_embeds_var": 2 * n_old + 1}   # RetrievalTables layout

@@ -153,6 +153,16 @@ class Base(abc.ABC):
     def _saved_arrays(self, path, model_name) -> dict:
         return dict(np.load(os.path.join(path, f"{model_name}_variables.npz")))
 
+    def _begin_rebuild(self, path, model_name):
+        """The opening of every `rebuild_model` (retraining on merged data): builds the new, larger model and returns
+        (the saved arrays, the `data_info` they were saved under)."""
+        old = self.data_info.old_info
+        if old is None:
+            raise ValueError("`rebuild_model` needs a `data_info` produced by `merge_trainset`")
+        self.build_model()
+        self.model_built = True
+        return self._saved_arrays(path, model_name), old
+
     def save(self, path, model_name, inference_only=False, **_):
         if getattr(self, "_dist", None) is not None:
             # one process per GPU: tables per shard, replicated parameters once (distributed.save_sharded); every rank calls

@@ -1,4 +1,5 @@
 from .dense import DenseStack, TFBatchNorm, TFDense, DenseParams
 from .embedding import FieldTables
+from .row_adam import NamedTables, RowAdam
 
-__all__ = ["DenseStack", "TFBatchNorm", "TFDense", "DenseParams", "FieldTables"]
+__all__ = ["DenseStack", "TFBatchNorm", "TFDense", "DenseParams", "FieldTables", "NamedTables", "RowAdam"]

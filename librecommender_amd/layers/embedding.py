@@ -18,6 +18,7 @@ from typing import Optional
 import torch
 
 from .. import ops
+from .row_adam import SegmentSpaces
 
 
 def glorot_uniform_(t: torch.Tensor, shape, gen: torch.Generator) -> None:
@@ -62,7 +63,7 @@ class FieldTables:
         if with_linear:
             self.lin_m = torch.zeros_like(self.lin)
             self.lin_v = torch.zeros_like(self.lin)
-        self._seg_builder: Optional[ops.SegmentBuilder] = None
+        self._spaces = SegmentSpaces(device)
         # global row range of every field [user, item, sparse columns...] (for lr_fm_field_stats_f32);
         # known when the caller passes the per-column offsets of the sparse table (all plain columns)
         self.field_row_start = None
@@ -93,10 +94,8 @@ class FieldTables:
         return torch.cat(cols, dim=1).contiguous()
 
     def segments(self, idx: torch.Tensor) -> ops.Segments:
-        n = idx.numel()
-        if self._seg_builder is None or self._seg_builder.n_max < n:
-            self._seg_builder = ops.SegmentBuilder(n, self.V, self.device)
-        return self._seg_builder.build(idx.reshape(-1))
+        """Of all `idx`, from the tables' one persistent builder: the next call overwrites what this one returned."""
+        return self._spaces.segments("rows", idx, self.V)
 
     def bytes(self) -> int:
         n = self.embed.numel() * 3

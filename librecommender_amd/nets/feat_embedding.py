@@ -25,6 +25,7 @@ from ..utils.device import to_device
 
 from .. import ops
 from ..layers import DenseParams, FieldTables
+from ..layers.row_adam import RowAdam
 
 
 @dataclass
@@ -96,7 +97,7 @@ class FeatEmbedding:
             P.add("embedding/dense_embeds_var", (spec.n_dense_cols, embed_size), "glorot_uniform")
             if with_linear:
                 P.add("embedding/dense_linear_var", (spec.n_dense_cols,), "glorot_uniform")
-        self._row_slot = None
+        self._adam = None
 
     def _i32(self, x):
         return to_device(x, self.device).to(torch.int32)
@@ -177,18 +178,13 @@ class FeatEmbedding:
         t = self.tables
         ids, g, gl = self._streams(ctx, extra, grads)
         seg = ops.build_segments(ids, t.V)
-        if not dense_adam:
-            ops.embed_scatter_adam(t.embed, t.m, t.v, g, seg, hp)
-            if gl is not None:
-                ops.embed_scatter_adam(t.lin, t.lin_m, t.lin_v, gl, seg, hp)
-            return
-        if self._row_slot is None:
-            self._row_slot = torch.full((t.V,), -1, dtype=torch.int32, device=self.device)
-        ops.adam_dense(t.embed, t.m, t.v, hp, grows=ops.embed_segment_sum(g, seg), seg=seg,
-                       row_slot=self._row_slot, l2=l2)
+        form = (bool(dense_adam), float(l2 or 0.0) if dense_adam else 0.0)     # the row-wise form has no l2 term: it is not passed on
+        if self._adam is None or (self._adam.dense, self._adam.l2) != form:     # (a net passes the same form every step)
+            self._adam = RowAdam(self.device, *form)
+        # two launches of the plain kernel, not `lin=`: that one has no long-run path, and these streams have Zipf heads
+        self._adam.update(hp, seg, t.embed, t.m, t.v, g)
         if gl is not None:
-            ops.adam_dense(t.lin, t.lin_m, t.lin_v, hp, grows=ops.embed_segment_sum(gl, seg), seg=seg,
-                           row_slot=self._row_slot, l2=l2)
+            self._adam.update(hp, seg, t.lin, t.lin_m, t.lin_v, gl)
 
     @torch.no_grad()
     def assign_oov(self, sparse_oov_rows):

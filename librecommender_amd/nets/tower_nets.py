@@ -17,6 +17,7 @@ from ..utils.device import to_device
 
 from .. import ops
 from ..layers import DenseParams, DenseStack, FieldTables
+from ..layers.row_adam import RowAdam
 
 
 class TwoTowerNet:
@@ -47,7 +48,15 @@ class TwoTowerNet:
         self.use_correction, self.remove_accidental_hits = use_correction, remove_accidental_hits
         self.lr, self.epsilon, self.step = lr, epsilon, 0
         self.out_dim = self.user_tower.n_out
-        self.dense_adam, self._row_slot = dense_adam, None   # True: TF1 semantics (every row decays each step)
+        self.adam = RowAdam(self.device, dense_adam, 0.0)    # dense: TF1 semantics (every row decays each step)
+
+    @property
+    def dense_adam(self):
+        return self.adam.dense
+
+    @dense_adam.setter
+    def dense_adam(self, on):
+        self.adam.dense = bool(on)
 
     # ---- index helpers ----------------------------------------------------------------------
     def _dev_i32(self, x):
@@ -169,14 +178,7 @@ class TwoTowerNet:
         loss.backward()
         with torch.no_grad():
             hp = self._hp()
-            seg = t.segments(idx)
-            if self.dense_adam:
-                if self._row_slot is None:
-                    self._row_slot = torch.full((t.V,), -1, dtype=torch.int32, device=self.device)
-                ops.adam_dense(t.embed, t.m, t.v, hp, grows=ops.embed_segment_sum(rows.grad.view(-1, self.K), seg),
-                               seg=seg, row_slot=self._row_slot)
-            else:
-                ops.embed_scatter_adam(t.embed, t.m, t.v, rows.grad.view(-1, self.K), seg, hp)
+            self.adam.update(hp, t.segments(idx), t.embed, t.m, t.v, rows.grad.view(-1, self.K))
             self.P.adam_step(hp)
         return loss.detach()
 

@@ -26,6 +26,7 @@ import torch.nn.functional as F
 from .. import ops
 from ..layers import DenseParams, DenseStack
 from ..layers.embedding import glorot_uniform_
+from ..layers.row_adam import RowAdam
 from ..utils.device import to_device
 from .feat_embedding import FeatSpec
 
@@ -49,19 +50,12 @@ class RetrievalTables:
             if rows:
                 glorot_uniform_(self.embed[off:off + rows], (rows, K), gen)
         self.m, self.v = torch.zeros_like(self.embed), torch.zeros_like(self.embed)
-        self._seg_builder = None
 
     def variable(self, name):
         spans = {"seq_embeds_var": (self.seq_off, self.n_items), "item_embeds_var": (self.item_off, self.n_items),
                  "sparse_embeds_var": (self.sparse_off, self.sparse_size)}
         off, n = spans[name]
         return self.embed[off:off + n]
-
-    def segments(self, ids):
-        n = ids.numel()
-        if self._seg_builder is None or self._seg_builder.n_max < n:
-            self._seg_builder = ops.SegmentBuilder(n, self.V, self.device)
-        return self._seg_builder.build(ids.reshape(-1))
 
 
 class YouTubeRetrievalNet:
@@ -85,12 +79,9 @@ class YouTubeRetrievalNet:
         # the short last batch of an epoch still draws `batch_size` classes
         self.batch_size = batch_size
         # tf.keras.regularizers.l2(reg) on the embedding variables adds 2 * reg * w to EVERY row's gradient each step
-        # (tfops/configs.py:20-26): representable only with the dense TF1 update
-        self.reg = float(reg or 0.0)
-        if self.reg and not dense_adam:
-            raise ValueError("`reg` regularises every embedding row each step (tf.keras.regularizers.l2 on the variables): "
-                             "use `dense_adam=True` with it; the row-wise Adam on touched rows cannot represent that term")
-        self.lr, self.epsilon, self.step, self.dense_adam, self._row_slot = lr, epsilon, 0, dense_adam, None
+        # (tfops/configs.py:20-26): representable only with the dense TF1 update (layers/row_adam.py)
+        self.adam = RowAdam(self.device, dense_adam, reg)
+        self.lr, self.epsilon, self.step = lr, epsilon, 0
         self.gen = torch.Generator(device=self.device)
         self.gen.manual_seed(seed)
 
@@ -198,13 +189,6 @@ class YouTubeRetrievalNet:
                     ids[-1] = torch.where(ids[-1] == bag[1], torch.full_like(ids[-1], -1), ids[-1])
             ids, g = torch.cat(ids).contiguous(), torch.cat(grads).contiguous()
             hp = self._hp()
-            seg = t.segments(ids)
-            if self.dense_adam:
-                if self._row_slot is None:
-                    self._row_slot = torch.full((t.V,), -1, dtype=torch.int32, device=self.device)
-                ops.adam_dense(t.embed, t.m, t.v, hp, grows=ops.embed_segment_sum(g, seg), seg=seg, row_slot=self._row_slot,
-                               l2=self.reg)
-            else:
-                ops.embed_scatter_adam(t.embed, t.m, t.v, g, seg, hp)
+            self.adam.update(hp, self.adam.segments("rows", ids, t.V), t.embed, t.m, t.v, g)
             self.P.adam_step(hp)
         return loss.detach()

@@ -38,6 +38,7 @@ class HipKernels:
 
         self.ops = ops
         self._builders = {}
+        self._row_slots = {}                         # the `row_slot` scratches of `adam_dense_rows`
 
     MAX_BUILDERS = 16
 
@@ -81,14 +82,11 @@ class HipKernels:
 
     def adam_dense_rows(self, table, m, v, grads, seg, hp, l2=0.0):
         """Dense (TF1) Adam over every row of `table`, the gradient rows `grads` [n, K] summed per row through `seg` first."""
-        key = (table.data_ptr(), table.shape[0])
-        slot = self._row_slots.get(key) if hasattr(self, "_row_slots") else None
-        if slot is None:
-            if not hasattr(self, "_row_slots"):
-                self._row_slots = {}
-            slot = self._row_slots[key] = torch.full((table.shape[0],), -1, dtype=torch.int32, device=table.device)
+        from .layers.row_adam import row_slot_of
+
         grows = self.ops.embed_segment_sum(grads.contiguous(), seg) if seg.n > 0 else None
-        self.ops.adam_dense(table, m, v, hp, grows=grows, seg=seg if seg.n > 0 else None, row_slot=slot, l2=l2)
+        self.ops.adam_dense(table, m, v, hp, grows=grows, seg=seg if seg.n > 0 else None,
+                            row_slot=row_slot_of(self._row_slots, table), l2=l2)
 
     def scatter_adam_lin(self, table, m, v, grads, lin, lin_m, lin_v, glin, seg, hp):
         """Owner-side update of a table and its linear weights from one pass over the received rows."""

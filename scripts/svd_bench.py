@@ -92,7 +92,7 @@ def ours(model, K, B, n_steps, users, items, labels, hist, dev):
             touched += torch.unique(idx[pos]).numel() / n_stat
     entries_ms = None
     if model == "svdpp":      # the entry list of a step alone (torch index ops and the step's one host read)
-        seg = net._segments("user", users[:B].contiguous(), N_USERS, want_slots=True)
+        seg = net.adam.segments("user", users[:B].contiguous(), N_USERS, want_slots=True)
         net._entries(seg, B)
         torch.cuda.synchronize()
         t = time.perf_counter()
