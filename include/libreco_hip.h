@@ -1059,6 +1059,42 @@ int lr_svdpp_hist_grad_f32(int mode, float* Y, float* m, float* v, int64_t n_ite
                            const int32_t* seg_rows, const int32_t* seg_start, const int32_t* n_seg, int64_t n,
                            float* grows, lr_adam_hp hp, void* ws, size_t ws_bytes, lr_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Recurrent layers — one GRU or LSTM layer of libreco/layers/recurrent.py:27-45 (the Keras layers of the TF2 branch with a
+ * sequence mask) over a padded, left-aligned batch, f32, D inputs and H units, both in [1, 128] (lr_rnn_supported,
+ * otherwise LR_ESHAPE).  No float atomics anywhere: same bits from run to run.
+ *   LR_RNN_GRU   Keras v2, reset_after: W [D, 3H], U [H, 3H], b [2, 3H], gate order z, r, h:
+ *                  mx = x_t W + b[0], mh = h U + b[1], z = sigmoid(mx_z + mh_z), r = sigmoid(mx_r + mh_r),
+ *                  c = act(mx_h + r * mh_h), h' = z * h + (1 - z) * c
+ *   LR_RNN_LSTM  W [D, 4H], U [H, 4H], b [4H], gate order i, f, c, o:  c' = f * c + i * act(.), h' = o * act(c')
+ *   `act` != 0: tanh; 0: the identity (the reference's activation=None under use_layer_norm).
+ * Input: x [B, L, D], or x == NULL and (table [V, D], ids int32 [B, L]) read in place (no [B, L, D] buffer is written).
+ * `lens` int32 [B] is clamped to [0, L].  Step t of sample b is MASKED when t >= lens[b], or on the table path when its id is
+ * outside [0, V): h (and c) are carried, hs[b, t] = the carried h (hs[:, L-1] is the last valid state; all 0 for lens = 0),
+ * the id is never dereferenced and the row it names is never used; gx is exactly 0 there.
+ * Dropout (nullable, constant over time, drawn and scaled by 1 / (1 - p) by the caller): x_t * in_mask [B, D] feeds the W
+ * product, h * rec_mask [B, H] feeds the U product only; the carry term z * h uses the unmasked state.
+ *   forward   writes every element of hs [B, L, H] and of `saved` (lr_rnn_fwd_saved_bytes(cell, B, L, H) bytes: the gates,
+ *             and the LSTM's cell state, that the backward reads), masked steps included.
+ *   backward  ghs [B, L, H] = the gradient with respect to every output step.  Writes every element of gx [B, L, D], gW, gU and
+ *             gb (the shapes of W, U, b).  The weight gradients are summed over B and L as per-chunk partials in `ws`
+ *             (lr_rnn_bwd_ws_bytes(cell, B, L, D, H) bytes, contents arbitrary on entry) added in chunk order.
+ * ---------------------------------------------------------------------------------- */
+#define LR_RNN_GRU 0
+#define LR_RNN_LSTM 1
+int lr_rnn_supported(int cell, int D, int H);
+size_t lr_rnn_fwd_saved_bytes(int cell, int64_t B, int L, int H);
+size_t lr_rnn_bwd_ws_bytes(int cell, int64_t B, int L, int D, int H);
+int lr_rnn_layer_fwd_f32(int cell, int act, const float* x, const float* table, int64_t V, const int32_t* ids,
+                         const int32_t* lens, int64_t B, int L, int D, int H, const float* W, const float* U,
+                         const float* b, const float* in_mask, const float* rec_mask, float* hs, void* saved,
+                         size_t saved_bytes, lr_stream_t stream);
+int lr_rnn_layer_bwd_f32(int cell, int act, const float* x, const float* table, int64_t V, const int32_t* ids,
+                         const int32_t* lens, int64_t B, int L, int D, int H, const float* W, const float* U,
+                         const float* in_mask, const float* rec_mask, const float* hs, const void* saved,
+                         const float* ghs, float* gx, float* gW, float* gU, float* gb, void* ws, size_t ws_bytes,
+                         lr_stream_t stream);
+
 /* Measurement probe (scripts/mfma_peak.py): iters x 8 back-to-back v_mfma_f32_32x32x2_f32 per wave on
  * 256 x waves_per_simd workgroups — the f32 MFMA rate the chip sustains at the clock it holds under that load. */
 int lr_mfma_f32_probe(int iters, int waves_per_simd, float* out, lr_stream_t stream);

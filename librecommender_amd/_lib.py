@@ -228,6 +228,13 @@ SIGNATURES = {
     "lr_svdpp_hist_grad_ws_bytes": (_sz, [_i64, _int]),
     "lr_svdpp_hist_grad_f32": (_int, [_int, _p, _p, _p, _i64, _int, _p, _p, _i64, _p, _p, _p, _p, _p, _i64, _p, AdamHP, _p,
                                       _sz, _p]),
+    "lr_rnn_supported": (_int, [_int, _int, _int]),
+    "lr_rnn_fwd_saved_bytes": (_sz, [_int, _i64, _int, _int]),
+    "lr_rnn_bwd_ws_bytes": (_sz, [_int, _i64, _int, _int, _int]),
+    "lr_rnn_layer_fwd_f32": (_int, [_int, _int, _p, _p, _i64, _p, _p, _i64, _int, _int, _int, _p, _p, _p, _p, _p, _p, _p, _sz,
+                                    _p]),
+    "lr_rnn_layer_bwd_f32": (_int, [_int, _int, _p, _p, _i64, _p, _p, _i64, _int, _int, _int, _p, _p, _p, _p, _p, _p, _p, _p,
+                                    _p, _p, _p, _p, _sz, _p]),
 }
 
 _lib = None

@@ -5,6 +5,7 @@ from .fm import FM, DeepFM
 from .item_cf import ItemCF
 from .lightgcn import LightGCN
 from .ngcf import NGCF
+from .rnn4rec import RNN4Rec
 from .sim import SIM
 from .svd import SVD
 from .svdpp import SVDpp
@@ -15,4 +16,4 @@ from .user_cf import UserCF
 from .youtube_ranking import YouTubeRanking
 from .youtube_retrieval import YouTubeRetrieval
 
-__all__ = ["ALS", "BPR", "DIN", "DeepFM", "FM", "ItemCF", "LightGCN", "NGCF", "SIM", "SVD", "SVDpp", "Swing", "Transformer", "TwoTower", "UserCF", "YouTubeRanking", "YouTubeRetrieval"]
+__all__ = ["ALS", "BPR", "DIN", "DeepFM", "FM", "ItemCF", "LightGCN", "NGCF", "RNN4Rec", "SIM", "SVD", "SVDpp", "Swing", "Transformer", "TwoTower", "UserCF", "YouTubeRanking", "YouTubeRetrieval"]

@@ -52,6 +52,14 @@ class DenseParams:
                 p.uniform_(-limit, limit, generator=self.gen)
             elif init == "ones":
                 p.fill_(1.0)
+            elif init == "orthogonal":          # tf.keras.initializers.Orthogonal: Q of a normal matrix, signs from diag(R)
+                rows, cols = shape
+                a = torch.randn((max(rows, cols), min(rows, cols)), generator=self.gen, device=self.device).cpu().double()
+                q, r = torch.linalg.qr(a)
+                q = q * torch.sign(torch.diagonal(r))
+                p.copy_((q.t() if rows < cols else q).float())
+            elif init == "lstm_bias":           # Keras `unit_forget_bias`: zeros, the forget gate (second quarter) ones
+                p[shape[0] // 4: shape[0] // 2].fill_(1.0)
             p.requires_grad_(True)
             p.grad = self.grad[off:off + n].view(shape)  # autograd accumulates in place here
             self.params[name] = p

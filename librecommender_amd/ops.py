@@ -2071,3 +2071,91 @@ def svdpp_hist_grad(G: torch.Tensor, scale: torch.Tensor, ent_slot: torch.Tensor
           _ptr(ent_slot), _ptr(seg.pos), _ptr(seg.rows), _ptr(seg.start), _ptr(seg.n_seg), seg.n, _ptr(grows),
           hp if hp is not None else adam_hp(0.0, 1), _ptr(ws), 0 if ws is None else ws.numel(), _stream())
     return grows
+
+
+# --------------------------------------------------------------------------------------
+# recurrent layers (csrc/rnn.hip)
+# --------------------------------------------------------------------------------------
+RNN_CELLS = {"gru": 0, "lstm": 1}
+
+
+def rnn_supported(cell: str, D: int, H: int) -> bool:
+    """Whether the recurrent-layer kernels take `D` inputs and `H` units for this cell."""
+    return cell in RNN_CELLS and bool(_lib.load().lr_rnn_supported(RNN_CELLS[cell], int(D), int(H)))
+
+
+def _rnn_check(cell, W, U, lens, x, table, ids, in_mask, rec_mask):
+    """-> (B, L, D, H, V) of one recurrent-layer call, its operands validated."""
+    if cell not in RNN_CELLS:
+        raise ValueError("cell must be `gru` or `lstm`")
+    G = 3 if cell == "gru" else 4
+    _req(W, torch.float32, "W", 2)
+    _req(U, torch.float32, "U", 2)
+    _req(lens, torch.int32, "lens", 1)
+    D, H = W.shape[0], U.shape[0]
+    if W.shape[1] != G * H or U.shape[1] != G * H:
+        raise ValueError(f"W must be [D, {G}H] and U [H, {G}H]")
+    if x is not None:
+        if table is not None or ids is not None:
+            raise ValueError("give either x or (table, ids)")
+        if _req(x, torch.float32, "x", 3).shape[2] != D:
+            raise ValueError("x must be [B, L, D]")
+        B, L, V = x.shape[0], x.shape[1], 0
+    else:
+        if table is None or ids is None:
+            raise ValueError("give either x or (table, ids)")
+        if _req(table, torch.float32, "table", 2).shape[1] != D:
+            raise ValueError("table must be [V, D]")
+        _req(ids, torch.int32, "ids", 2)
+        B, L, V = ids.shape[0], ids.shape[1], table.shape[0]
+    if lens.numel() != B:
+        raise ValueError("lens must hold one length per sample")
+    for t_, n_, w_ in ((in_mask, "in_mask", D), (rec_mask, "rec_mask", H)):
+        if t_ is not None and _req(t_, torch.float32, n_, 2).shape != (B, w_):
+            raise ValueError(f"{n_} must be [B, {w_}]")
+    return B, L, D, H, V
+
+
+def rnn_layer_fwd(cell: str, W: torch.Tensor, U: torch.Tensor, b: torch.Tensor, lens: torch.Tensor,
+                  x: Optional[torch.Tensor] = None, table: Optional[torch.Tensor] = None, ids: Optional[torch.Tensor] = None,
+                  in_mask: Optional[torch.Tensor] = None, rec_mask: Optional[torch.Tensor] = None, act: bool = True):
+    """`lr_rnn_layer_fwd_f32`: one GRU / LSTM layer over x [B, L, D] or over the rows table[ids] read in place.  Returns
+    (hs [B, L, H], saved): every output step (a masked step repeats the carried state) and what `rnn_layer_bwd` reads."""
+    B, L, D, H, V = _rnn_check(cell, W, U, lens, x, table, ids, in_mask, rec_mask)
+    G = 3 if cell == "gru" else 4
+    if _req(b, torch.float32, "b").numel() != (2 if cell == "gru" else 1) * G * H:
+        raise ValueError("b must be [2, 3H] for the GRU and [4H] for the LSTM")
+    c = RNN_CELLS[cell]
+    hs = torch.empty((max(B, 1), L, H), dtype=torch.float32, device=W.device)[:B]
+    nbytes = _lib.load().lr_rnn_fwd_saved_bytes(c, B, L, H)
+    saved = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=W.device)
+    _call("lr_rnn_layer_fwd_f32", c, 1 if act else 0, _ptr(x), _ptr(table), V, _ptr(ids), _ptr(lens), B, L, D, H, _ptr(W), _ptr(U),
+          _ptr(b), _ptr(in_mask), _ptr(rec_mask), _ptr(hs), _ptr(saved), saved.numel() * 4, _stream())
+    return hs, saved
+
+
+def rnn_layer_bwd(cell: str, W: torch.Tensor, U: torch.Tensor, lens: torch.Tensor, hs: torch.Tensor, saved: torch.Tensor,
+                  ghs: torch.Tensor, x: Optional[torch.Tensor] = None, table: Optional[torch.Tensor] = None,
+                  ids: Optional[torch.Tensor] = None, in_mask: Optional[torch.Tensor] = None,
+                  rec_mask: Optional[torch.Tensor] = None, act: bool = True):
+    """`lr_rnn_layer_bwd_f32`: from ghs [B, L, H] (the gradient of every output step) -> (gx [B, L, D], gW, gU, gb); gx is
+    exactly 0 at masked steps, the weight gradients are summed in a fixed order."""
+    B, L, D, H, V = _rnn_check(cell, W, U, lens, x, table, ids, in_mask, rec_mask)
+    G = 3 if cell == "gru" else 4
+    _req(hs, torch.float32, "hs", 3)
+    _req(saved, torch.float32, "saved", 1)
+    if _req(ghs, torch.float32, "ghs", 3).shape != (B, L, H) or hs.shape != (B, L, H):
+        raise ValueError("hs and ghs must be [B, L, H]")
+    c = RNN_CELLS[cell]
+    if saved.numel() * 4 < _lib.load().lr_rnn_fwd_saved_bytes(c, B, L, H):
+        raise ValueError("saved is not the forward's buffer for this shape")
+    dev = W.device
+    gx = torch.empty((max(B, 1), L, D), dtype=torch.float32, device=dev)[:B]
+    gW = torch.empty((D, G * H), dtype=torch.float32, device=dev)
+    gU = torch.empty((H, G * H), dtype=torch.float32, device=dev)
+    gb = torch.empty((2, G * H) if cell == "gru" else (G * H,), dtype=torch.float32, device=dev)
+    ws = torch.empty(max(_lib.load().lr_rnn_bwd_ws_bytes(c, B, L, D, H), 256), dtype=torch.uint8, device=dev)
+    _call("lr_rnn_layer_bwd_f32", c, 1 if act else 0, _ptr(x), _ptr(table), V, _ptr(ids), _ptr(lens), B, L, D, H, _ptr(W), _ptr(U),
+          _ptr(in_mask), _ptr(rec_mask), _ptr(hs), _ptr(saved), _ptr(ghs), _ptr(gx), _ptr(gW), _ptr(gU), _ptr(gb), _ptr(ws),
+          ws.numel(), _stream())
+    return gx, gW, gU, gb
