@@ -289,6 +289,22 @@ constexpr float kFiltDelta = 0.004f;
 constexpr float kNormUp = 1.0009765625f;
 using s16x4 = __attribute__((ext_vector_type(4))) short;
 constexpr float kBf16Up = 1.00390625f;      // >= (1 + 2^-9) (elements rounded to bf16) x (1 + 2^-10)
+// Below the normal range the relative bound is not the whole error, and the norms themselves are not to be trusted: a square below
+// 2^-126 is subnormal or 0 in the f32 sums of a norm, and the MFMA / v_dot2 may flush subnormal operands, products and partial
+// sums (not measured: taken as flushed, a flushed operand is 0 and a subnormal partial sum may be 0).  What is lost that way is
+// ABSOLUTE: < 2^-126 per term, < 2^-118 over the <= 129 terms of a score or of a squared norm.
+//   A squared norm n2 >= kFiltMinN2 = 2^-64, as computed, is trusted: the true one is within n2 (1 + 2^-54) (no square that
+//   contributes to it is subnormal), and for a pair of trusted rows |u| |i| >= 2^-64, so that the 2^-118 lost from `approx` is
+//   2^-54 |u| |i| — nothing beside the 2 % (2^-13.6) that kFiltDelta spares.  (The proof needs 2^-100; 2^-64 leaves 2^36.)
+//   A row whose squared norm comes out BELOW 2^-64 has a true norm < 2^-31.9, whatever underflowed in the sum, and takes
+//   kFiltNormFloor = 2^-20 in place of its norm: |approx - exact| <= |approx| + |exact| <= 2.02 |u| |i| < 2^-30.8 |u| for the
+//   other row u, and delta |u| 2^-20 > 2^-28 |u| covers it (delta > 2^-8) — as does delta 2^-20 |i| when it is the user that is
+//   floored, and delta 2^-40 when both are; the smallest such term, 2^-8 2^-20 2^-32 = 2^-60, is far above the 2^-118.
+// An all-zero row (padding, OOV) is floored too: its bound is delta |u| 2^-20 instead of 0, which costs it nothing (approx =
+// exact = 0) and the others a candidate slot only for users whose k'-th bound is below 4e-9 |u|.  Rows of squared norm >= 2^-64
+// are untouched: one compare + select per row beside its 32 x 32 scores.  (tests/test_filter_bound_cpu.py carries both constants.)
+constexpr float kFiltMinN2 = 0x1p-64f;
+constexpr float kFiltNormFloor = 0x1p-20f;
 __device__ __forceinline__ uint32_t bf16_up(float x) {     // x >= 0 (or inf / NaN) rounded UP to bf16, as the 16 high bits
   const uint32_t u = __float_as_uint(x);
   return (u + ((u & 0xffffu) ? 0x10000u : 0u)) >> 16;
@@ -317,7 +333,7 @@ __device__ __forceinline__ float dpp_add(float v) {
 // empty); a workgroup all of whose slots are empty returns at once.  Lists, thresholds and outputs are indexed by SLOT.
 // AR 2 scores are UPPER BOUNDS of the exact scores: one more k-block carries delta |u| (user side) and |i| (item side: v_dot2 over the
 // row's bf16 fragments as they are read for the MFMAs), both rounded UP to bf16, so that the accumulator ends as
-// approx + delta |u| |i|  >=  exact  (kFiltDelta).
+// approx + delta |u| |i|  >=  exact  (kFiltDelta; a norm too small to be trusted is replaced by kFiltNormFloor, see kFiltMinN2).
 // `maxn2` (AR 2, nullable): set to 1 when a staged row's norm is not finite (the bound does not hold for it).
 template <int DT, int WU, int AR = 0, int TU = 1, bool MASKED = false>
 __global__ __launch_bounds__((TkShape<DT, WU, AR, TU>::NW * 64), (TkShape<DT, WU, AR, TU>::OCC)) void score_topk_kernel(
@@ -437,7 +453,7 @@ __global__ __launch_bounds__((TkShape<DT, WU, AR, TU>::NW * 64), (TkShape<DT, WU
       }
       if constexpr (AR == 2) {
         un2 += __shfl_xor(un2, 32);                         // the other half of the user's row
-        const uint32_t du = bf16_up(kFiltDelta * sqrtf(un2) * kNormUp);
+        const uint32_t du = bf16_up(un2 < kFiltMinN2 ? kFiltDelta * kFiltNormFloor : kFiltDelta * sqrtf(un2) * kNormUp);   // (kFiltMinN2: the floor)
         ubx[t] = s16x4{static_cast<short>(h == 0 ? du : 0u), 0, 0, 0};
       }
     }
@@ -719,8 +735,9 @@ __global__ __launch_bounds__((TkShape<DT, WU, AR, TU>::NW * 64), (TkShape<DT, WU
           const auto sw = __builtin_amdgcn_permlane32_swap(rb, rb, false, false);
           const float n2 = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
           bad_norm |= !(n2 < INFINITY);            // inf, NaN, overflow: the bound does not hold
-          // (v_sqrt_f32: 1 ulp, inside kBf16Up's spare)
-          const s16x4 ax = {static_cast<short>(h == 0 ? bf16_up(__builtin_amdgcn_sqrtf(n2) * kBf16Up) : 0u), 0, 0, 0};
+          // (v_sqrt_f32: 1 ulp, inside kBf16Up's spare; a norm below the range in which it can be trusted: the floor, kFiltMinN2)
+          const float ni = n2 < kFiltMinN2 ? kFiltNormFloor : __builtin_amdgcn_sqrtf(n2) * kBf16Up;
+          const s16x4 ax = {static_cast<short>(h == 0 ? bf16_up(ni) : 0u), 0, 0, 0};
 #pragma unroll
           for (int t = 0; t < TU; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x8bf16_1k(ax, ubx[t], acc[t], 0, 0, 0);   // (k = 8: two-register operands)
         }
@@ -1309,9 +1326,12 @@ static int score_topk_impl(const float* users, int64_t B, const float* items, in
 //   3. users that are not certified (dense near-ties: more than k' items within the bound's width of the k-th score) are re-run
 //      by the exact kernel (MASKED instantiation: workgroups none of whose users failed leave at once) and their rows replaced.
 //      A catalogue holding a row whose norm is not finite certifies nobody.
-// The returned scores are f32 dot products of their pairs and the ids those of the exact ranking, whatever the data; what the
-// data decides is only how many users take the slow path (none on the bench's shape: k' = 256 for k = 100 leaves ~60 spare
-// candidates beyond the ~195 the bound needs at 10^8 N(0, 1) items x 128).
+//      A user or an item whose f32 squared norm is below 2^-64 (squares underflow there, and the hardware may flush subnormal
+//      operands and sums) enters the bound with the norm 2^-20 instead (kFiltMinN2): the bound stays one, only looser.
+// The returned scores are f32 dot products of their pairs and the ids those of the exact ranking for every catalogue and batch of
+// finite f32 rows whose squared norms are finite in f32 (rows that are not certify nobody, see 3.) — rows of tiny or zero norm
+// and subnormal elements included; what the data decides is only how many users take the slow path (none on the bench's shape:
+// k' = 256 for k = 100 leaves ~60 spare candidates beyond the ~195 the bound needs at 10^8 N(0, 1) items x 128).
 // ======================================================================================================================
 constexpr int64_t kFiltMinItems = int64_t(1) << 20;
 

@@ -249,7 +249,15 @@ class DeepFMTail:
             gz1 = torch.outer(self.gl, wd)
             sgz1 = gz1.sum(0)
         self._flush_deferred()
-        return self.loss_sum[0], self.gl, gz1, sgz1
+        return self._step_loss(), self.gl, gz1, sgz1
+
+    def _step_loss(self) -> torch.Tensor:
+        """This step's mean loss.  `loss_sum` belongs to the buffer set and is overwritten by the next step on it: an eager step
+        returns a copy of its own (a caller may keep the losses of an epoch and average them afterwards).  Under stream capture
+        the view itself is returned — a captured step holds kernel nodes only (`GraphRunner.check_kernel_nodes_only`), and
+        whoever replays the graph copies its static output once."""
+        loss = self.loss_sum[0]
+        return loss if torch.cuda.is_current_stream_capturing() else loss.clone()
 
     def check(self) -> None:
         """Raise `TailBarrierError` if a one-launch step on any of this tail's buffer sets gave up on a grid barrier (the
@@ -315,4 +323,4 @@ class DeepFMTail:
             self._reduce(self.db_partial[i], 0, w[i + 1], P[lay.b].grad, defer=True)
         self._reduce(self.sgz_partial, 0, w[0], self.sgz1, defer=True)
         self._flush_deferred()
-        return self.loss_sum[0], self.gl, self.gz1, self.sgz1
+        return self._step_loss(), self.gl, self.gz1, self.sgz1

@@ -390,6 +390,12 @@ class ShardedFieldTables:
         # files in place could leave a new `embed` beside old moments under the old meta); its orphans go with the next save.
         import glob
 
+        # (a save interrupted between writing the meta temporary and its rename leaves the temporary behind: under its
+        # former name `<stem>.tmp.npz` it matched the loaders' `<name>_shard*of*.npz` and made the set look one shard too many)
+        meta_tmp = stem + ".meta.tmp"
+        for f in (meta_tmp, stem + ".tmp.npz"):
+            if os.path.exists(f):
+                os.remove(f)
         tag = 1
         if os.path.exists(stem + ".npz"):
             try:
@@ -401,14 +407,26 @@ class ShardedFieldTables:
             tmp = f"{stem}.s{tag}.{k}.tmp.npy"
             np.save(tmp, getattr(self, k).cpu().numpy())
             os.replace(tmp, f"{stem}.s{tag}.{k}.npy")
-        tmp = stem + ".tmp.npz"
-        np.savez(tmp, V=np.int64(self.V), K=np.int64(self.K), rank=np.int64(self.rank), world=np.int64(self.world),
-                 keys=np.asarray(keys), tag=np.int64(tag))
-        os.replace(tmp, stem + ".npz")
+        with open(meta_tmp, "wb") as fh:            # (a file object: given a name, savez would append `.npz` to it)
+            np.savez(fh, V=np.int64(self.V), K=np.int64(self.K), rank=np.int64(self.rank), world=np.int64(self.world),
+                     keys=np.asarray(keys), tag=np.int64(tag))
+        os.replace(meta_tmp, stem + ".npz")
         for f in glob.glob(glob.escape(stem) + ".*.npy"):           # other tags, the untagged files of earlier layouts
             if not os.path.basename(f).startswith(os.path.basename(stem) + f".s{tag}."):
                 os.remove(f)
         return stem + ".npz"
+
+    @staticmethod
+    def shard_meta_files(path: str, name: str) -> list:
+        """The meta files `<name>_shard<r>of<W>.npz` under `path`, sorted — and nothing else the pattern happens to match (the
+        meta temporary of an interrupted save used to be `<name>_shard<r>of<W>.tmp.npz`)."""
+        import glob
+        import os
+        import re
+
+        pat = re.compile(re.escape(name) + r"_shard\d+of\d+\.npz")
+        return sorted(f for f in glob.glob(os.path.join(glob.escape(path), f"{glob.escape(name)}_shard*of*.npz"))
+                      if pat.fullmatch(os.path.basename(f)))
 
     @staticmethod
     def shard_array(path: str, name: str, r: int, w: int, key: str, meta, mmap: bool = False):
@@ -451,12 +469,11 @@ class ShardedFieldTables:
         row r // W_old and goes to local row r // W of rank r % W here.  Every rank memory-maps every old shard and reads
         only the rows it owns.  All `W_old` files of ONE world size must be present; the `rank` / `world` stored in each
         file are checked against its name."""
-        import glob
         import os
 
         import numpy as np
 
-        files = sorted(glob.glob(os.path.join(path, f"{name}_shard*of*.npz")))
+        files = self.shard_meta_files(path, name)
         if not files:
             raise FileNotFoundError(f"no {name}_shard*of*.npz under {path}")
         worlds = {int(f.rsplit("of", 1)[1].split(".")[0]) for f in files}
@@ -489,12 +506,11 @@ class ShardedFieldTables:
         """Retraining under a process group (`tfops/rebuild.py:12-139`): global row src[i] of a sharded checkpoint of the
         OLD (smaller) table becomes global row dst[i] of this table; rows not named keep their fresh initialisation, moments
         of new rows stay zero.  The old shards are memory-mapped; every rank reads only the rows it will own."""
-        import glob
         import os
 
         import numpy as np
 
-        files = sorted(glob.glob(os.path.join(path, f"{name}_shard*of*.npz")))
+        files = self.shard_meta_files(path, name)
         worlds = {int(f.rsplit("of", 1)[1].split(".")[0]) for f in files}
         if len(worlds) != 1 or len(files) != next(iter(worlds), -1):
             raise ValueError(f"{path}: expected the complete {name} shard set of ONE world size, found {len(files)} files of "

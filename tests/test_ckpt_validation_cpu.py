@@ -125,3 +125,58 @@ def test_interrupted_save_leaves_the_previous_checkpoint_whole(tmp_path, monkeyp
 
     with pytest.raises(FileNotFoundError, match="missing"):
         r.load_shard(str(tmp_path))
+
+
+def test_stale_meta_temporary_does_not_hide_a_checkpoint(tmp_path):
+    """A `save_shard` that died between writing its meta temporary and the rename left `<stem>.tmp.npz` behind, which the
+    `<name>_shard*of*.npz` pattern of `load_shards_resharded` / `load_shards_mapped` counted as a third shard of two ("3 of 2
+    shards found"): the intact previous checkpoint could not be loaded.  The temporary is now `<stem>.meta.tmp`, both loaders
+    take meta files by their exact name only (a temporary of the former name may still lie about), and the next save of the
+    rank removes both."""
+    import numpy as np
+    import torch
+
+    from librecommender_amd.parallel import ShardedFieldTables
+
+    class _NoGroup(ShardedFieldTables):          # rank r of w without a process group
+        def __init__(self, V, K, rank=0, world=1):
+            self.V, self.K, self.rank, self.world, self.device = V, K, rank, world, torch.device("cpu")
+            n = len(range(rank, V, world))
+            self.embed, self.m, self.v = torch.zeros((n, K)), torch.zeros((n, K)), torch.zeros((n, K))
+            self.lin, self.lin_m, self.lin_v = torch.zeros((n, 1)), torch.zeros((n, 1)), torch.zeros((n, 1))
+
+    V, K = 11, 3
+    full = {k: torch.arange(V * w, dtype=torch.float32).reshape(V, w) + 1000.0 * j
+            for j, (k, w) in enumerate((("embed", K), ("m", K), ("v", K), ("lin", 1), ("lin_m", 1), ("lin_v", 1)))}
+    savers = [_NoGroup(V, K, r, 2) for r in range(2)]
+    for t in savers:
+        for k, a in full.items():
+            setattr(t, k, a[t.rank::2].clone())           # global row g lives in shard g % 2 at local row g // 2
+        t.save_shard(str(tmp_path))
+    src, dst = np.array([0, 3, 4, 10]), np.array([7, 1, 12, 2])      # old global row -> row of a table grown to 13 rows
+
+    def load_both():
+        a = _NoGroup(V, K)
+        a.load_shards_resharded(str(tmp_path))
+        b = _NoGroup(13, K)
+        b.load_shards_mapped(str(tmp_path), "tables", src, dst, V)
+        return [getattr(a, k).clone() for k in full] + [getattr(b, k).clone() for k in full]
+
+    clean = load_both()
+    for k, got in zip(full, clean):                        # (the loaders themselves: every row where it belongs)
+        assert torch.equal(got, full[k])
+    for k, got in zip(full, clean[len(full):]):
+        assert torch.equal(got[dst], full[k][src])
+    before = sorted(p.name for p in tmp_path.iterdir())
+    old_tmp, new_tmp = tmp_path / "tables_shard1of2.tmp.npz", tmp_path / "tables_shard1of2.meta.tmp"
+    np.savez(str(old_tmp), V=np.int64(V), K=np.int64(K), rank=np.int64(1), world=np.int64(2), keys=np.asarray(["embed"]), tag=np.int64(9))
+    new_tmp.write_bytes(old_tmp.read_bytes()[:40])         # cut short, as an interrupted write leaves it
+    for got, want in zip(load_both(), clean):
+        assert torch.equal(got, want)
+    # the next save of that rank clears both away and leaves no temporary of its own
+    savers[1].save_shard(str(tmp_path))
+    after = sorted(p.name for p in tmp_path.iterdir())
+    assert after == [n.replace("shard1of2.s1.", "shard1of2.s2.") for n in before]
+    assert not [n for n in after if "tmp" in n]
+    for got, want in zip(load_both(), clean):
+        assert torch.equal(got, want)

@@ -72,3 +72,49 @@ def test_din_fit_graph_equals_eager(dev, device_sampling):
     rec_g = g.recommend_user(info.id2user[0], 7)
     rec_e = e.recommend_user(info.id2user[0], 7)
     np.testing.assert_array_equal(rec_g[info.id2user[0]], rec_e[info.id2user[0]])
+
+
+@pytest.mark.parametrize("algo,graph_step", [("DeepFM", False), ("DIN", False), ("FM", None), ("DeepFM", True), ("DIN", True)])
+def test_a_steps_loss_is_that_steps_own_value(dev, capsys, algo, graph_step):
+    """The hand-written tail reduces the loss into one persistent scalar of its buffer set (layers/tail.py: `loss_sum`).  An
+    eager step used to return a VIEW of it: every loss a caller kept became the last step's, and `Trainer.run`, which stacks
+    the epoch's losses, printed the last step's loss as `train_loss`.  Every step's loss is read right after the step and
+    again after the epoch: the kept tensors must still hold what they held (eager steps; the replayed graph, whose static output
+    `train_on_batch` copies; FM, whose loss comes from autograd), and the printed `train_loss` is the mean of the steps."""
+    import re
+
+    from librecommender_amd.algorithms import FM
+
+    cls = {"DeepFM": DeepFM, "DIN": DIN, "FM": FM}[algo]
+    df, ucols, icols = feat_frame(n=160, nu=40, ni=30)                       # 160 positives + 160 sampled negatives: 5 steps of 64
+    if algo == "DIN":
+        train, info = DatasetPure.build_trainset(df[["user", "item", "label", "time"]])
+        kw = dict(recent_num=12, hidden_units=(128, 64, 32), graph_step=graph_step)
+    else:
+        train, info = DatasetFeat.build_trainset(df, user_col=ucols, item_col=icols, sparse_col=ucols + icols, dense_col=[])
+        kw = dict(hidden_units=(128, 64, 32), graph_step=graph_step) if algo == "DeepFM" else {}
+    model = cls("ranking", info, embed_size=64, n_epochs=1, lr=1e-2, batch_size=64, num_neg=1, sampler="random", seed=7, **kw)
+    kept, recorded = [], []
+    step = model.train_on_batch
+
+    def recording_step(b, **kwargs):
+        loss = step(b, **kwargs)
+        recorded.append(float(loss))                  # this step's value, read before the next step runs
+        kept.append(loss)
+        return loss
+
+    model.train_on_batch = recording_step
+    np.random.seed(1)
+    torch.manual_seed(1)
+    model.fit(train, neg_sampling=True, verbose=2, shuffle=True)
+    torch.cuda.synchronize()
+    if algo == "DeepFM":
+        assert model.net.hip_tail and bool(getattr(model.net, "_use_graph", False)) == graph_step
+        assert not graph_step or sum("graph" in st for st in model.net._graphs.values()) == 1
+    if algo == "DIN":
+        assert model.net._fstep is not None and model.net.graph_step == graph_step
+        assert not graph_step or sum("graph" in st for st in model.net._fstep.runner.graphs.values()) == 1
+    assert len(recorded) == 5 and len(set(recorded)) == 5, recorded          # (five different losses: an alias would show)
+    assert [float(t) for t in kept] == recorded
+    printed = re.search(r"train_loss: ([-0-9.e]+|nan)", capsys.readouterr().out)
+    assert printed is not None and float(printed.group(1)) == round(float(np.mean(recorded)), 4), (printed, recorded)

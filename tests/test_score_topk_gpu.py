@@ -352,6 +352,95 @@ def test_filter_never_loses_a_winner_hidden_by_bf16_rounding(dev):
     assert int(failed.sum()) == B
 
 
+_UNDERFLOW_CASE = {}
+
+
+def _underflow_case(dev):
+    """The adversarial catalogue of `test_filter_keeps_the_winners_where_the_norms_underflow`, its fp64 top k and the scores of
+    the unscaled run: built once, shared by the scaled cases, never modified."""
+    key = str(dev)
+    if key in _UNDERFLOW_CASE:
+        return _UNDERFLOW_CASE[key]
+    D, k, N, B, n_dec = 64, 16, 40_000, 64, 3000
+    g = torch.Generator(device=dev).manual_seed(19)
+    U = torch.ones((B, D), device=dev) * (1 + torch.arange(B, device=dev)[:, None] / 128.0)
+    I = torch.randn((N, D), device=dev, generator=g) * 0.01
+    j = (torch.rand((n_dec, D), device=dev, generator=g) < 0.2).float()
+    j[:, 0] = 1
+    I[:n_dec] = 1 + 2.0 ** -7 + j * 2.0 ** -7                                 # bf16 values: approx == exact
+    win = torch.arange(n_dec, n_dec + k, device=dev)
+    I[win] = 1 + 2.0 ** -7 + 2.0 ** -8 - 2.0 ** -12                           # just below a rounding midpoint: approx < exact
+    for r in range(k):
+        I[n_dec + r, :r] = 1 + 2.0 ** -7 + 2.0 ** -8 - 2.0 ** -11             # (distinct scores)
+    assert torch.equal(U.bfloat16().float(), U) and torch.equal(I[:n_dec].bfloat16().float(), I[:n_dec])
+    P = U.double() @ I.double().T
+    ref = torch.sort(torch.topk(P, k, dim=1).indices, 1).values
+    assert torch.equal(ref, win[None, :].expand(B, k)), "the fp64 top k of every user must be exactly the winners"
+    kp = ops._lib.load().lr_score_topk_filter_kp(k)
+    assert kp == 88
+    Pb = U.bfloat16().double() @ I.bfloat16().double().T
+    assert int(torch.topk(Pb, kp, dim=1).indices.max()) < n_dec, "a bf16 ranking must hold decoys only in its first k' places"
+    s0, i0, f0 = _filtered(U, I, k)
+    _UNDERFLOW_CASE[key] = (U, I, k, ref, s0.clone())
+    return _UNDERFLOW_CASE[key]
+
+
+@pytest.mark.parametrize("a,b", [(0, 0), (-40, -40), (-55, -55), (-60, 0), (-70, 0), (-80, 0), (-80, 40), (0, -80), (40, -80)])
+def test_filter_keeps_the_winners_where_the_norms_underflow(dev, a, b):
+    """Users x 2^a, items x 2^b on a catalogue that fools a bf16 ranking (3,000 decoys that are bf16 values against 16 winners
+    whose bf16 images round down): a power of two changes neither the fp64 ranking nor an f32 product that stays normal — the
+    scores are ordinary f32 numbers in every case (2^-74 .. 2^-34 at 2^-80) — but the f32 SQUARES of a row's norm underflow below
+    2^-75, and with them went the term delta |u| |i| of the filter's bound while the bf16 rounding error of the approximate score
+    stayed: every user was certified on decoys only.  The norm floor (kFiltMinN2, csrc/score_topk.hip) keeps the bound a bound:
+    more than k' items sit inside its width, nobody is certified, the exact pass returns the fp64 top k."""
+    U, I, k, ref, s0 = _underflow_case(dev)
+    Us, Is = (U * 2.0 ** a).contiguous(), (I * 2.0 ** b).contiguous()
+    assert torch.equal(Us.double() * 2.0 ** -a, U.double()) and torch.equal(Is.double() * 2.0 ** -b, I.double())     # (exact scalings)
+    s, i, failed = _filtered(Us, Is, k)
+    n_wrong = int((torch.sort(i, 1).values != ref).any(1).sum())
+    print(f"scales 2^{a}, 2^{b}: {n_wrong} of {U.shape[0]} users with a wrong id set, {int(failed.sum())} not certified")
+    assert torch.equal(torch.sort(i, 1).values, ref)
+    assert int(failed.sum()) == U.shape[0]
+    torch.testing.assert_close(s, s0 * 2.0 ** (a + b), rtol=2e-6, atol=0.0)
+
+
+def _random_case_b(dev):
+    """The random catalogue of case (b) of `test_filter_falls_back_where_the_bound_proves_nothing`."""
+    g = torch.Generator(device=dev).manual_seed(1)
+    B, N, D, k = 200, 60_000, 128, 20
+    U, I = torch.randn((B, D), device=dev, generator=g), torch.randn((N, D), device=dev, generator=g)
+    U[:, 0] = 0
+    return U, I, k
+
+
+def test_filter_certifies_beside_all_zero_rows(dev):
+    """Every tenth item row all-zero (padding, OOV rows): approx = exact = 0 for them, their norm of 0 is no sign of underflow.
+    A rule that took them for untrustworthy rows through a catalogue-wide flag would certify nobody: everybody is certified."""
+    U, I, k = _random_case_b(dev)
+    I[::10] = 0
+    s, i, failed = _filtered(U, I, k)
+    assert int(failed.sum()) == 0
+    se, ie = _exact(U, I, k)
+    assert torch.equal(torch.sort(i, 1).values, torch.sort(ie, 1).values)
+
+
+def test_one_tiny_user_and_one_tiny_item_cost_one_user_the_proof(dev):
+    """One user row and one item row x 2^-80 in a random catalogue: the floored norms are per row.  The tiny user cannot be
+    certified (every score lies inside delta 2^-20 |i|) and takes the exact pass; the tiny item's bound, delta |u| 2^-20, is no
+    candidate for anybody; all others are certified as without the two rows.  Id sets equal the exact kernel's wherever the exact
+    k-th and (k+1)-th scores are separated."""
+    U, I, k = _random_case_b(dev)
+    U[17] *= 2.0 ** -80
+    I[4321] *= 2.0 ** -80
+    s, i, failed = _filtered(U, I, k)
+    print(f"not certified: {int(failed.sum())} of {U.shape[0]} users")
+    se, ie = _exact(U, I, k + 1)
+    sep = (se[:, k - 1] - se[:, k]) > 1e-5 * se[:, :k].abs().max(dim=1).values
+    assert float(sep.float().mean()) > 0.9 and bool(sep[17])
+    assert torch.equal(torch.sort(i[sep], 1).values, torch.sort(ie[sep, :k], 1).values)
+    assert int(failed[17]) == 1 and int(failed.sum()) == 1
+
+
 def test_filter_shapes_outside_its_range_run_the_exact_kernel(dev):
     g = torch.Generator(device=dev).manual_seed(3)
     for D, k in ((16, 10), (128, 101), (128, 300), (200, 10)):
