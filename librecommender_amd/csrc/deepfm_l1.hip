@@ -33,16 +33,6 @@ namespace lr {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
-// Profiling builds only (scripts/lab/r04/ablate.sh compiles this file with -DLR_L1_ABLATE=<bits> into a separate
-// library loaded through LIBRECO_HIP_LIB): parts of the wide forward kernel are switched off to see what its time is
-// made of.  1: every gather reads row 0 (no HBM latency)  2: weights never refilled (no L2 stream)  4: no barrier
-// 8: no LDS staging traffic  16: no MFMA.  The product build defines nothing: kAblate == 0 folds every test away.
-#ifndef LR_L1_ABLATE
-#define LR_L1_ABLATE 0
-#endif
-constexpr int kAblate = LR_L1_ABLATE;
-
-
 __device__ __forceinline__ f32x16 acc_zero() {
   return f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 }
@@ -464,7 +454,7 @@ __global__ __launch_bounds__(kBlock, 1) void l1_fwd64_kernel(
   auto row_load = [&](auto set_c, int u) {                   // HBM -> registers, branch-free (every lane of a row loads `lin`: one request)
     constexpr int set = decltype(set_c)::value;
     const bool ok = pid[u] < Vu;
-    const uint32_t id = (ok && !(kAblate & 1)) ? pid[u] : 0u;
+    const uint32_t id = ok ? pid[u] : 0u;
     pre_ok[set] = (pre_ok[set] & ~(1u << u)) | (ok ? (1u << u) : 0u);
     pre[set][u] = ld4(table + static_cast<uint64_t>(id) * KD + c4);
     if (kLin) prel[set][u] = lin[id];
@@ -476,7 +466,7 @@ __global__ __launch_bounds__(kBlock, 1) void l1_fwd64_kernel(
     const float4 x = ok ? pre[set][u] : f4_zero();
     S[u] = f4_add(S[u], x);
     Q[u] = f4_fma(x, x, Q[u]);
-    if (!(kAblate & 8)) st4(dst + (srow + u * RPP) * LDW + c4, x);
+    st4(dst + (srow + u * RPP) * LDW + c4, x);
     if (kLin) *reinterpret_cast<float*>(id_slot(srow + u * RPP, f)) = ok ? prel[set][u] : 0.f;
   };
 
@@ -490,17 +480,10 @@ __global__ __launch_bounds__(kBlock, 1) void l1_fwd64_kernel(
   };
   auto frag_read = [&](int f, auto set_c, int s, int q) {
     constexpr int set = decltype(set_c)::value;
-    if ((kAblate & 8) && f > 1) return;
     a[set][s][q] = ld4(rows + (f & 1) * TS * LDW + (s * 32 + j) * LDW + h * KH + q * 4);
   };
   auto mfma_group = [&](auto set_c, int q) {
     constexpr int set = decltype(set_c)::value;
-    if (kAblate & 16) {
-#pragma unroll
-      for (int c = 0; c < NC; ++c)
-        asm volatile("" ::"v"(a[set][0][q].x), "v"(a[set][1][q].w), "v"(bw[set][c][q].x), "v"(bw[set][c][q].w));
-      return;
-    }
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
       acc[c][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[set][0][q].x, bw[set][c][q].x, acc[c][0], 0, 0, 0);
@@ -518,7 +501,6 @@ __global__ __launch_bounds__(kBlock, 1) void l1_fwd64_kernel(
   // only in program order, so twenty VALU / DS instructions in ONE gap leave the pipe idle behind them): after every
   // MFMA up to four of {VALU, SALU, VMEM, DS}.
   auto spread = [&]() {
-    if (kAblate & 32) return;
 #pragma unroll
     for (int i = 0; i < 8 * NC; ++i) {
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -541,7 +523,7 @@ __global__ __launch_bounds__(kBlock, 1) void l1_fwd64_kernel(
 #pragma unroll
     for (int q = 0; q < HQ; ++q) {                 // ---- first half of the chain
       mfma_group(SP{}, q);
-      if (has2 && !(kAblate & 2)) {
+      if (has2) {
 #pragma unroll
         for (int c = 0; c < NC; ++c) bw[P][c][q] = ld4(wn[c] + q * 256);
       }
@@ -553,11 +535,11 @@ __global__ __launch_bounds__(kBlock, 1) void l1_fwd64_kernel(
       spread();
       __builtin_amdgcn_sched_barrier(0);
     }
-    if (!(kAblate & 4)) __syncthreads();           // rows of field f+1 visible (buffer (f+1)&1 was last read one field ago)
+    __syncthreads();                              // rows of field f+1 visible (buffer (f+1)&1 was last read one field ago)
 #pragma unroll
     for (int q = HQ; q < NQ; ++q) {                // ---- second half
       mfma_group(SP{}, q);
-      if (has2 && !(kAblate & 2)) {
+      if (has2) {
 #pragma unroll
         for (int c = 0; c < NC; ++c) bw[P][c][q] = ld4(wn[c] + q * 256);
       }

@@ -43,16 +43,8 @@ using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
 constexpr int SB_KD = 64, SB_H1 = 128;                 // the compiled shape
 constexpr int SB_THREADS = 512;
 
-// Profiling builds only (scripts/lab/r05/ablate_build.sh compiles this file with -DLR_SB_ABLATE=<bits> into a separate library
-// loaded through LIBRECO_HIP_LIB): 1: every gather reads row 0 (no HBM latency / traffic)  2: no MFMA  4: the row-gradient
-// kernel stores nothing  8: weight planes never refilled (no L2 -> CU weight stream)  16: the multiplying waves read no
-// fragments from LDS  32: the staging waves write nothing to LDS  64: no barriers.  The product build defines nothing.
-#ifndef LR_SB_ABLATE
-#define LR_SB_ABLATE 0
-#endif
-constexpr int kSbAblate = LR_SB_ABLATE;
 __device__ __forceinline__ void sb_sync() {
-  if (!(kSbAblate & 64)) __syncthreads();
+  __syncthreads();
 }
 
 __device__ __forceinline__ void split3(f32x8 x, bf16x8& a1, bf16x8& a2, bf16x8& a3) {
@@ -91,10 +83,6 @@ __device__ __forceinline__ void split8(float4 lo, float4 hi, bf16x8& a1, bf16x8&
 }
 // acc += a * b with a = a1 + a2 + a3, b = b1 + b2 + b3: the six largest cross terms, smallest first
 __device__ __forceinline__ void mfma6(f32x16& acc, bf16x8 a1, bf16x8 a2, bf16x8 a3, bf16x8 b1, bf16x8 b2, bf16x8 b3) {
-  if (kSbAblate & 2) {
-    asm volatile("" : "+v"(acc) : "v"(a1), "v"(a2), "v"(a3), "v"(b1), "v"(b2), "v"(b3));
-    return;
-  }
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, b1, acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b3, acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b2, acc, 0, 0, 0);
@@ -257,7 +245,7 @@ __global__ __launch_bounds__(SB_THREADS, (TS == 64 ? 4 : 2)) void l1_fwd_sb_kern
       const bf16x8* ar = al + buf * AF + g * 32 + ((j + 2 * kb + g) & 31);         // the rotated slot of this lane's row
 #pragma unroll
       for (int p = 0; p < 3; ++p)
-        if (!(kSbAblate & 16)) dst[p] = ar[((t * KB + kb) * 3 + p) * 64];
+        dst[p] = ar[((t * KB + kb) * 3 + p) * 64];
     };
     sb_sync();                                    // fields 0 / 1 staged
 #pragma unroll
@@ -276,10 +264,8 @@ __global__ __launch_bounds__(SB_THREADS, (TS == 64 ? 4 : 2)) void l1_fwd_sb_kern
           // MFMA of the next field then waits for an L2 round trip) and reads fragments right in front of their MFMAs
           __builtin_amdgcn_sched_barrier(0);
         }
-        if (!(kSbAblate & 8)) {
 #pragma unroll
-          for (int p = 0; p < 3; ++p) bq[kb][p] = bnext[(kb * CT * 3 + p) * 64];
-        }
+        for (int p = 0; p < 3; ++p) bq[kb][p] = bnext[(kb * CT * 3 + p) * 64];
         __builtin_amdgcn_sched_barrier(0);
       }
       sb_sync();
@@ -352,7 +338,7 @@ __global__ __launch_bounds__(SB_THREADS, (TS == 64 ? 4 : 2)) void l1_fwd_sb_kern
 #pragma unroll
       for (int u = 0; u < NLD; ++u) {
         const bool ok = static_cast<uint32_t>(idn[set][u]) < Vu;
-        const uint32_t id = (ok && !(kSbAblate & 1)) ? static_cast<uint32_t>(idn[set][u]) : 0u;
+        const uint32_t id = ok ? static_cast<uint32_t>(idn[set][u]) : 0u;
         if (ok) pre_ok[set] |= 1u << u;
         pre[set][u] = ld4(table + static_cast<uint64_t>(id) * KD + c4);
       }
@@ -373,12 +359,9 @@ __global__ __launch_bounds__(SB_THREADS, (TS == 64 ? 4 : 2)) void l1_fwd_sb_kern
         Q[u] = f4_fma(x, x, Q[u]);
         uint2 p1, p2, p3;
         split4(x, p1, p2, p3);
-        if (kSbAblate & 32) asm volatile("" :: "v"(p1.x), "v"(p2.x), "v"(p3.x), "v"(p1.y), "v"(p2.y), "v"(p3.y));
-        else {
-          *reinterpret_cast<uint2*>(da + a_off(u)) = p1;
-          *reinterpret_cast<uint2*>(da + a_off(u) + 1024) = p2;
-          *reinterpret_cast<uint2*>(da + a_off(u) + 2048) = p3;
-        }
+        *reinterpret_cast<uint2*>(da + a_off(u)) = p1;
+        *reinterpret_cast<uint2*>(da + a_off(u) + 1024) = p2;
+        *reinterpret_cast<uint2*>(da + a_off(u) + 2048) = p3;
       }
       if (kLin && l_mine) lin_out[b0 * F + f_lo + l_off + i] = prel_ok[set] ? prel[set] : 0.f;
     };
@@ -568,8 +551,7 @@ __global__ __launch_bounds__(SB_THREADS, 2) void l1_dgrad_sb_kernel(
 #pragma unroll
     for (int r = r0; r < r0 + 2; ++r) {
       const float v = a[r] + fm[r];
-      if (kSbAblate & 4) asm volatile("" :: "v"(v), "v"(dst[r]));
-      else *reinterpret_cast<float*>(reinterpret_cast<char*>(ge) + dst[r]) = v;
+      *reinterpret_cast<float*>(reinterpret_cast<char*>(ge) + dst[r]) = v;
     }
   };
   // one field: its chain into `acc`, the pending set `prev` stored two rows per k-block
@@ -584,7 +566,7 @@ __global__ __launch_bounds__(SB_THREADS, 2) void l1_dgrad_sb_kernel(
       if (kb + 1 < KBH) {
 #pragma unroll
         for (int p = 0; p < 3; ++p)
-          if (!(kSbAblate & 16)) wf[(kb + 1) & 1][p] = wr[((kb + 1) * NT * 3 + p) * 64];
+          wf[(kb + 1) & 1][p] = wr[((kb + 1) * NT * 3 + p) * 64];
       }
       mfma6(acc, g1[kb], g2[kb], g3[kb], wf[kb & 1][0], wf[kb & 1][1], wf[kb & 1][2]);
       if constexpr (decltype(has_prev)::value) store2(prev, 2 * kb);
@@ -598,12 +580,12 @@ __global__ __launch_bounds__(SB_THREADS, 2) void l1_dgrad_sb_kernel(
   // step f: planes / slots of field f + 1 requested; chain of field f (stores of field f - 1 in its shadow); slots of field f
   // read (all reads of the buffer are in front of the barrier); field f + 1 written into the other buffer; barrier.
   auto step = [&](int f, int buf, f32x16& acc, const f32x16& prev, auto has_prev) {
-    if (f + 1 < f_hi && !(kSbAblate & 8)) stage_load(f + 1);
+    if (f + 1 < f_hi) stage_load(f + 1);
     __builtin_amdgcn_sched_barrier(0);
     chain(buf, acc, prev, has_prev);
     slots_read(buf);
     __builtin_amdgcn_sched_barrier(0);
-    if (f + 1 < f_hi && !(kSbAblate & 8)) stage_write(buf ^ 1);
+    if (f + 1 < f_hi) stage_write(buf ^ 1);
     sb_sync();
   };
   int f = f_lo;
@@ -682,11 +664,8 @@ __global__ __launch_bounds__((CW + 4) * 64, (CW + 4) / 4) void l1_wgrad_sb_kerne
       for (int p = 0; p < NP; ++p) {
         const float* src = rows + rb * RSZ + (pq[p] * TSW + sl * 16 + 8 * g) * KD + pm[p] * 32 + j;
         float4 lo, hi;
-        if (!(kSbAblate & 16)) {
         lo.x = src[0 * KD]; lo.y = src[1 * KD]; lo.z = src[2 * KD]; lo.w = src[3 * KD];
         hi.x = src[4 * KD]; hi.y = src[5 * KD]; hi.z = src[6 * KD]; hi.w = src[7 * KD];
-        }
-        if (kSbAblate & 16) { lo = f4_zero(); hi = f4_zero(); asm volatile("" : "+v"(lo.x), "+v"(hi.x)); }
         split8(lo, hi, dst[p][0], dst[p][1], dst[p][2]);
       }
     };
@@ -758,7 +737,7 @@ __global__ __launch_bounds__((CW + 4) * 64, (CW + 4) / 4) void l1_wgrad_sb_kerne
       for (int u = 0; u < NLD; ++u) {
         const int64_t b = stc * TSW + srow + 16 * (u & 1);
         const bool ok = f_ok[u] && b < B && static_cast<uint32_t>(idn[set][u]) < Vu;
-        const uint32_t id = (ok && !(kSbAblate & 1)) ? static_cast<uint32_t>(idn[set][u]) : 0u;
+        const uint32_t id = ok ? static_cast<uint32_t>(idn[set][u]) : 0u;
         if (ok) pre_ok[set] |= 1u << u;
         pre[set][u] = ld4(table + static_cast<uint64_t>(id) * KD + c4);
       }

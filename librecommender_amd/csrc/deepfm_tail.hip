@@ -79,8 +79,8 @@ __device__ __forceinline__ f32x16 tile_zero() { return f32x16{0, 0, 0, 0, 0, 0, 
 
 // Staging loops: q = tid, tid + 256, ... < n; `load(q)` reads global memory, `store(q, v)` consumes the value.  U loads are issued
 // before the first value is used — written as a plain loop (load, use, load, use ...) every iteration pays a full memory round
-// trip: 8-32 serialized L2 / HBM latencies per staging loop were what the tail's kernels spent their time on (round 5:
-// scripts/lab/r05/tail_marks.py — the 128 <- 64 backward tile took 52 us with 4 us of MFMA work in it).
+// trip: 8-32 serialized L2 / HBM latencies per staging loop were what the tail's kernels spent their time on (round 5,
+// profiles/r05_l1_split_bf16.md — the 128 <- 64 backward tile took 52 us with 4 us of MFMA work in it).
 template <int U, typename T, typename L, typename S>
 __device__ __forceinline__ void staged_loop(int n, L load, S store) {
   for (int base = threadIdx.x; base < n; base += U * kBlock) {
@@ -131,7 +131,7 @@ __device__ __forceinline__ float bn_act(float z, const BnRef& bn, int c, float& 
 // The same with the column's parameters in registers: the staging loops below give a thread ONE column whenever the width
 // divides the workgroup size (q = tid + 256 k -> column tid % d), so the four / five parameter loads per ELEMENT (flat loads
 // from LDS in the fused tail) become loads per thread.  Same arithmetic, same bits.  (Round 5: the elementwise staging, not the
-// products, is what the tail's time was made of — scripts/lab/r05/tail_marks.py.)
+// products, is what the tail's time was made of — profiles/r05_l1_split_bf16.md.)
 struct BnCol { float mean, inv, gamma, beta; bool on; };
 __device__ __forceinline__ BnCol bn_col(const BnRef& bn, int c) {
   BnCol b{0.f, 0.f, 0.f, 0.f, bn.mean != nullptr};

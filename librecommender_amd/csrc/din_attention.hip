@@ -467,10 +467,8 @@ __global__ __launch_bounds__(kBlock) void din_reduce_kernel(const float* __restr
   }
 }
 
-#ifndef LR_DIN_GRID_MULT
-#define LR_DIN_GRID_MULT 2     // workgroups per CU the attention kernels' persistent grids are capped at (profiling switch)
-#endif
-static inline int din_grid(int64_t B) { return grid_for(B, kBlock / kWave, kNumCU * LR_DIN_GRID_MULT); }
+constexpr int kDinGridMult = 2;     // workgroups per CU the attention kernels' persistent grids are capped at
+static inline int din_grid(int64_t B) { return grid_for(B, kBlock / kWave, kNumCU * kDinGridMult); }
 
 static inline size_t din_fwd_lds(int K, int L) { return (size_t(4) * K * kH + 4 * size_t(L)) * 4; }
 static inline size_t din_bwd_lds(int K, int L) {
@@ -781,9 +779,3 @@ extern "C" int lr_din_build_ids_i32(const int32_t* users, const int32_t* items, 
                      users, items, sparse, sparse_ld, cols, n_plain, seqs, lens, B, L, user_off, item_off, sparse_off, ids);
   return lr::launch_status();
 }
-
-#ifdef LR_DIN_MARKS
-extern "C" int lr_din_debug_marks(unsigned long long* out64) {
-  return static_cast<int>(hipMemcpyFromSymbol(out64, HIP_SYMBOL(lr::lr_din_marks), 64 * sizeof(unsigned long long)));
-}
-#endif

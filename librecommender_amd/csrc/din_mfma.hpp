@@ -412,26 +412,12 @@ __global__ __launch_bounds__(kBlock, 2) void din_fwd_mfma_kernel(
 // =================================================================================================
 constexpr int kDinSmall = 2 * kDH + 4;
 
-// Lab builds (-DLR_DIN_MARKS, scripts/lab/r06/din_marks.sh): wave 0 of workgroup 1 of the data kernel leaves shader-clock time
-// stamps of its first two samples' phases in lr_din_marks (read back by lr_din_debug_marks).  The product build has none of it.
-#ifdef LR_DIN_MARKS
-__device__ unsigned long long lr_din_marks[64];
-#define LR_DIN_MARK(i) do { if (blockIdx.x == 1 && threadIdx.x == 0 && (i) < 64) lr_din_marks[(i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define LR_DIN_MARK(i) do { } while (0)
-#endif
-#ifndef LR_DIN_BWD_WAVES
-#define LR_DIN_BWD_WAVES 2     // waves per SIMD the attention backward kernels are compiled for (profiling: 3 / 4 spill)
-#endif
-#ifndef LR_DIN_P1_TILES
-#define LR_DIN_P1_TILES 2      // key tiles of the first backward pass in flight together (4, same box: 0.1605 vs 0.1576 ms)
-#endif
-#ifndef LR_DIN_BWD_WAVES_H
-#define LR_DIN_BWD_WAVES_H 2   // the same for the form that reads the saved hidden activations
-#endif
+constexpr int kDinBwdWaves = 2;     // waves per SIMD the attention backward kernels are compiled for (profiling: 3 / 4 spill)
+constexpr int kDinP1Tiles = 2;      // key tiles of the first backward pass in flight together (4, same box: 0.1605 vs 0.1576 ms)
+constexpr int kDinBwdWavesH = 2;    // the same for the form that reads the saved hidden activations
 // SAVED_H: h = sigmoid(z) comes from the forward's `hid` buffer instead of being recomputed (no forward weight images, no zq)
 template <int NT, bool GATHER, bool SAVED_H = false>
-__global__ __launch_bounds__(kBlock, SAVED_H ? LR_DIN_BWD_WAVES_H : LR_DIN_BWD_WAVES) void din_bwd_data_kernel(
+__global__ __launch_bounds__(kBlock, SAVED_H ? kDinBwdWavesH : kDinBwdWaves) void din_bwd_data_kernel(
     const float* __restrict__ qsrc, const float* __restrict__ ksrc, int64_t V,
     const int32_t* __restrict__ item, const int32_t* __restrict__ seq, const int32_t* __restrict__ len,
     int64_t B, int L, const float* __restrict__ W1, const float* __restrict__ b1,
@@ -446,7 +432,6 @@ __global__ __launch_bounds__(kBlock, SAVED_H ? LR_DIN_BWD_WAVES_H : LR_DIN_BWD_W
   // SAVED_H: the sample's query and output-gradient rows live in LDS during the second pass (one copy per lane group: every
   // key lane of a group holds the same 16-byte piece) instead of in 64 VGPRs
   float4* sqg_all = reinterpret_cast<float4*>(sda_all + 4 * ((L + 3) & ~3));   // [4 waves][2][NT][4]
-  LR_DIN_MARK(0);
   if (SAVED_H && order != nullptr) {       // the forward's extra workgroup left the images behind `hid`: a coalesced 24 KB copy
     const float4* timg = reinterpret_cast<const float4*>(hid + static_cast<int64_t>(B) * L * kDH);
     for (int q = threadIdx.x; q < 3 * NT * 64; q += kBlock) Tw[q] = timg[q];
@@ -454,8 +439,6 @@ __global__ __launch_bounds__(kBlock, SAVED_H ? LR_DIN_BWD_WAVES_H : LR_DIN_BWD_W
     din_stage_weights<NT, true, !SAVED_H>(W1, F, Tw);    // (SAVED_H never reads the forward-type images)
   }
   __syncthreads();
-  LR_DIN_MARK(1);
-  int mark_s = 0;
 
   const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
   const int i = lane & 15, kq = lane >> 4;
@@ -475,7 +458,6 @@ __global__ __launch_bounds__(kBlock, SAVED_H ? LR_DIN_BWD_WAVES_H : LR_DIN_BWD_W
   const int64_t nwaves = static_cast<int64_t>(gridDim.x) * (kBlock / kWave);
   for (int64_t slot = static_cast<int64_t>(blockIdx.x) * (kBlock / kWave) + wid; slot < B; slot += nwaves) {
     const int64_t b = order != nullptr ? order[slot] : slot;
-    LR_DIN_MARK(2 + 8 * mark_s);
     int n = len[b];
     n = n < 0 ? 0 : (n > L ? L : n);
     float4 q4[NT], go4[NT];
@@ -504,14 +486,13 @@ __global__ __launch_bounds__(kBlock, SAVED_H ? LR_DIN_BWD_WAVES_H : LR_DIN_BWD_W
       for (int r = 0; r < 4; ++r) zq[r] += b1r[r];
     }
     const int tiles = (n + 15) >> 4;
-    LR_DIN_MARK(3 + 8 * mark_s);
 
     // pass 1: da_l = <gout, key_l>, dot = sum_l a_l da_l
-    // (LR_DIN_P1_TILES tiles per trip: their rows are requested together — the walk is bound by the latency of random row reads,
+    // (kDinP1Tiles tiles per trip: their rows are requested together — the walk is bound by the latency of random row reads,
     // one wave holds one sample, and a sample of 17 - 32 keys exposes that latency once instead of twice; per lane the sums are
     // taken in the same ascending key order as before.  Four tiles per trip measured 3 us slower than two.)
     float dotp = 0.f;
-    constexpr int TP = SAVED_H ? LR_DIN_P1_TILES : 2;   // tiles whose rows are requested together (the recomputing form keeps q4 live: 2)
+    constexpr int TP = SAVED_H ? kDinP1Tiles : 2;   // tiles whose rows are requested together (the recomputing form keeps q4 live: 2)
     for (int T = 0; T < tiles; T += TP) {
       bool okv[TP], actv[TP];
       const float* kpv[TP];
@@ -549,7 +530,6 @@ __global__ __launch_bounds__(kBlock, SAVED_H ? LR_DIN_BWD_WAVES_H : LR_DIN_BWD_W
       }
     }
     const float dot = row_sum16(dotp);
-    LR_DIN_MARK(4 + 8 * mark_s);
 
     // pass 2
     float4 dq4[NT];
@@ -655,10 +635,6 @@ __global__ __launch_bounds__(kBlock, SAVED_H ? LR_DIN_BWD_WAVES_H : LR_DIN_BWD_W
         for (int u = 0; u < NT; ++u) st4(gkey + pos * K + 16 * u + 4 * kq, f4_zero());
       }
     }
-    LR_DIN_MARK(5 + 8 * mark_s);
-#ifdef LR_DIN_MARKS
-    if (blockIdx.x == 1 && threadIdx.x == 0) lr_din_marks[7 + 8 * mark_s] = static_cast<unsigned long long>(n);
-#endif
     // Dz_j = sum over the sample's keys; d q += (W1a+W1c) Dz
 #pragma unroll
     for (int r = 0; r < 4; ++r) Dz[r] = row_sum16(Dz[r]);
@@ -678,10 +654,7 @@ __global__ __launch_bounds__(kBlock, SAVED_H ? LR_DIN_BWD_WAVES_H : LR_DIN_BWD_W
       o.w = row_sum16(dq4[u].w) + g[3];
       if (i == 0) st4(gq + b * K + 16 * u + 4 * kq, o);
     }
-    LR_DIN_MARK(6 + 8 * mark_s);
-    ++mark_s;
   }
-  LR_DIN_MARK(60);
   // per-wave partials of db1 | dW2 | db2 (sum over this wave's keys = lanes of a row)
   float* sm = small + (static_cast<int64_t>(blockIdx.x) * (kBlock / kWave) + wid) * kDinSmall;
 #pragma unroll
@@ -703,7 +676,7 @@ __global__ __launch_bounds__(kBlock, SAVED_H ? LR_DIN_BWD_WAVES_H : LR_DIN_BWD_W
 // through LDS to get the reduction index (the key) off the lane axis.
 // =================================================================================================
 template <int NT, bool GATHER>
-__global__ __launch_bounds__(kBlock, LR_DIN_BWD_WAVES) void din_bwd_param_kernel(
+__global__ __launch_bounds__(kBlock, kDinBwdWaves) void din_bwd_param_kernel(
     const float* __restrict__ qsrc, const float* __restrict__ ksrc, int64_t V,
     const int32_t* __restrict__ item, const int32_t* __restrict__ seq, const int32_t* __restrict__ len,
     int64_t B, int L, const float* __restrict__ dzbuf, const float* __restrict__ Dzbuf,

@@ -30,6 +30,8 @@
 //               planes are split once into registers, and a 32 x 32 x 16 block of the contraction is six
 //               v_mfma_f32_32x32x16_bf16 (192 matrix-pipe cycles against 512 for eight v_mfma_f32_32x32x2_f32).  Scores agree
 //               with the f32 chain to f32 rounding (not bit for bit): tests pin both against fp64.
+//   Filter    : the one-term bf16 form (AR 2, lr_score_topk_filter_f32, described at its entry point below).  Same decomposition
+//               with 64-row stages (kFiltRS sub-tiles per wave) and, above 128 users, two 32-user tiles per wave (TU = 2).
 //   Order     : (score desc, id asc) — total order, so results are run-to-run identical and
 //               independent of the tiling.  NaN scores are dropped.
 #include <stdlib.h>
@@ -41,49 +43,25 @@ namespace lr {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
-#ifndef LR_TOPK_WIN_ROWS
-#define LR_TOPK_WIN_ROWS 256
-#endif
-#ifndef LR_TOPK_WIN_SLACK
-#define LR_TOPK_WIN_SLACK 1
-#endif
 constexpr int kPD = 2;      // stages of item prefetch in flight
+constexpr int kWinRows = 256;   // lockstep window: 12 ranges per XCD x (1 + slack) windows x rows x 512 B against the 4 MB L2
+constexpr int kWinSlack = 1;    // windows a workgroup may run ahead of the slowest one of its range
 // The one-term filter (AR 2) has 1/6 of the split form's MFMA work per stage: with 32-row stages its loop is bound by the latency
-// of the item loads (a stage's loads are issued one iteration before they are written to LDS).  It therefore takes LR_TK_RS
+// of the item loads (a stage's loads are issued one iteration before they are written to LDS).  It therefore takes kFiltRS
 // 32-row sub-tiles per wave and stage (more bytes in flight per workgroup, fewer stage hand-overs per item row).
-#ifndef LR_TK_RS
-#define LR_TK_RS 2          // (measured at 1,024 users x 100 M x 128, k' = 256: 46.5 ms with 1, 44.6 with 2, 86.9 with 4 — one workgroup per CU)
-#endif
-#ifndef LR_TK_NB
-#define LR_TK_NB 3
-#endif
-#ifndef LR_TK_RS_NARROW
-#define LR_TK_RS_NARROW 0
-#endif
-#ifndef LR_TK_RS8
-#define LR_TK_RS8 4         // the eight-wave form: 128-row stages (four sub-tiles per wave)
-#endif
-#ifndef LR_TK_NB8
-#define LR_TK_NB8 3
-#endif
-#ifndef LR_TK_W8
-#define LR_TK_W8 0          // 1: batches above 128 users run the eight-wave form of the filter
-#endif
-#ifndef LR_TK_OCC
-#define LR_TK_OCC 2         // (its 64-row stages: two workgroups per CU by LDS at a reduction width of 128)
-#endif
+constexpr int kFiltRS = 2;      // (measured at 1,024 users x 100 M x 128, k' = 256: 46.5 ms with 1, 44.6 with 2, 86.9 with 4 — one workgroup per CU)
+constexpr int kFiltNB = 3;      // its stage buffers in the LDS ring
+constexpr int kFiltOCC = 2;     // (its 64-row stages: two workgroups per CU by LDS at a reduction width of 128)
+constexpr int kFiltTU = 2;      // its 32-user tiles per wave when the batch fills them (above 128 users)
+constexpr int kFiltWGs = 2;     // its workgroups per CU the grid is planned for: one round of them
 template <int DT, int WU, int AR, int TU = 1>
 struct TkShape {
-  // 32-row item sub-tiles per wave and stage.  The filter: 32 LR_TK_RS rows per stage.  The exact forms at narrow reduction
-  // widths (a 32-row stage of 16 floats is 2 KB: the hand-over of a stage costs more than its MFMAs): 128 rows at DT = 16, 64 at 32
-  // WU == 8 (the filter only): workgroups of EIGHT waves, one user tile each, sharing a staged stage — the registers a wave saves on
-  // user fragments (32 instead of 64) hold a second accumulator set: the threshold tests of one sub-tile run under the MFMAs
-  // of the next
-  static constexpr int NW = WU == 8 ? 8 : 4;                                   // waves per workgroup
-  static constexpr int RSW = AR == 2 ? (WU == 8 ? LR_TK_RS8 : LR_TK_RS) : (LR_TK_RS_NARROW && DT <= 32) ? 64 / DT : 1;
+  // 32-row item sub-tiles per wave and stage: the filter 32 kFiltRS rows per stage, the exact forms 32
+  static constexpr int NW = 4;                                                 // waves per workgroup
+  static constexpr int RSW = AR == 2 ? kFiltRS : 1;
   static constexpr int RS = RSW * WU >= NW ? RSW * WU / NW : 1;
-  static constexpr int NB = AR == 2 ? (WU == 8 ? LR_TK_NB8 : LR_TK_NB) : (DT <= 128 ? 3 : 2);          // stage buffers in the LDS ring
-  static constexpr int OCC = AR == 2 ? (WU == 8 ? 1 : LR_TK_OCC) : AR == 1 ? 2 : DT <= 128 ? 3 : 1;   // workgroups per CU the registers are cut for
+  static constexpr int NB = AR == 2 ? kFiltNB : (DT <= 128 ? 3 : 2);          // stage buffers in the LDS ring
+  static constexpr int OCC = AR == 2 ? kFiltOCC : AR == 1 ? 2 : DT <= 128 ? 3 : 1;   // workgroups per CU the registers are cut for
   static constexpr int TI = 32 * (NW / WU) * RS;                               // item rows per stage
 };
 constexpr int kRing = 32;   // per-wave candidate ring entries (LDS)
@@ -117,15 +95,7 @@ static TopkPlan make_plan(int64_t B, int64_t N, int D, int k, int arith = 0) {
   p.WI = 4 / p.WU;
   // the one-term filter: two user tiles per wave (a staged item row then feeds twice the MFMA work: the filter's loop is bound by
   // instruction issue, not by the matrix pipe) and a merge over twice the keys (its k' is ~2.5 k)
-#ifndef LR_TK_TU_MAX
-#define LR_TK_TU_MAX 2
-#endif
-  p.TU = (arith == 2 && B > 128) ? LR_TK_TU_MAX : 1;
-  if (arith == 2 && B > 128 && LR_TK_W8) {           // eight waves per workgroup, one user tile each
-    p.WU = 8;
-    p.WI = 1;
-    p.TU = 1;
-  }
+  p.TU = (arith == 2 && B > 128) ? kFiltTU : 1;
   const int merge_keys = arith == 2 ? 2 * kMergeKeys : kMergeKeys;
   p.n_ut = static_cast<int>(ceil_div(B, 32 * p.WU * p.TU));
   p.B_pad = static_cast<int64_t>(p.n_ut) * 32 * p.WU * p.TU;
@@ -134,10 +104,7 @@ static TopkPlan make_plan(int64_t B, int64_t N, int D, int k, int arith = 0) {
   // of user planes) and was measured with its own one-round grid as well (G = 2 * 256 / n_ut: 146.1 ms per 100 M x 1,024 pass
   // against 141.1 ms with this one, GPU calls r06 topk_sb_time): it keeps the same plan, and the same workspace.
   // (the one-term filter holds two workgroups per CU: one round of them)
-#ifndef LR_TK_WGS2
-#define LR_TK_WGS2 2
-#endif
-  int64_t G = ceil_div((arith == 2 ? (p.WU == 8 ? 1 : LR_TK_WGS2) : 3) * kNumCU, p.n_ut);
+  int64_t G = ceil_div((arith == 2 ? kFiltWGs : 3) * kNumCU, p.n_ut);
   // One merge block holds gl lists' keys in registers; above that the lists are merged in groups of gl and the groups with one
   // another (two launches): up to gl^2 lists.  Small batches (one or two user tiles) need many more item ranges than gl to put a
   // workgroup on every CU — with G <= gl a batch of <= 64 users streamed 100 M items through 80 workgroups (39 ms; 73 ms in the
@@ -310,16 +277,6 @@ __device__ __forceinline__ uint32_t bf16_up(float x) {     // x >= 0 (or inf / N
   return (u + ((u & 0xffffu) ? 0x10000u : 0u)) >> 16;
 }
 
-// Lab builds (-DLR_TK_MARKS): every wave of the filter kernel adds the shader-clock time it spent per phase of the stage loop
-// (0 waiting for the stage, 1 MFMAs + epilogues, 2 waiting for the ring slot, 3 waiting for the prefetch + writing the stage,
-// 4 stages, 5 the window-edge lockstep) to lr_tk_marks; read back with lr_score_topk_debug_marks.
-#ifdef LR_TK_MARKS
-__device__ unsigned long long lr_tk_marks[8];
-#define LR_TK_T() __builtin_amdgcn_s_memtime()
-#else
-#define LR_TK_T() 0ull
-#endif
-
 // v + (v of the lane the DPP control names; 0 for the rows outside ROWS)
 template <int CTRL, int ROWS>
 __device__ __forceinline__ float dpp_add(float v) {
@@ -358,7 +315,7 @@ __global__ __launch_bounds__((TkShape<DT, WU, AR, TU>::NW * 64), (TkShape<DT, WU
   constexpr int DH = DT / 2;          // dims per lane half
   constexpr int LDW = DT + 4;         // padded LDS row (floats)
   static_assert(TU == 1 || AR == 2, "several user tiles per wave: the one-term filter only");
-  constexpr int kTI = TkShape<DT, WU, AR, TU>::TI;   // item rows per stage: one 32-row sub-tile per wave (AR 2: LR_TK_RS of them)
+  constexpr int kTI = TkShape<DT, WU, AR, TU>::TI;   // item rows per stage: one 32-row sub-tile per wave (AR 2: kFiltRS of them)
   constexpr int SUBS = kTI / 32;
   constexpr int NB = TkShape<DT, WU, AR, TU>::NB;    // stage buffers in the LDS ring (3 workgroups/CU fit; SB: 2)
   constexpr int NQ = kTI * DT / 4;            // float4 slots per stage
@@ -475,11 +432,7 @@ __global__ __launch_bounds__((TkShape<DT, WU, AR, TU>::NW * 64), (TkShape<DT, WU
   int32_t cr0[TU], cr1[TU], cr2[TU], cr3[TU];
 #pragma unroll
   for (int t = 0; t < TU; ++t) {
-#ifdef LR_TK_LAB_NOCONS
-    const bool filt = false && consumed_ptr != nullptr && consumed_idx != nullptr &&
-#else
     const bool filt = user_ok[t] && consumed_ptr != nullptr && consumed_idx != nullptr &&
-#endif
                       (filter_flag == nullptr || filter_flag[urow[t]] != 0);
     c_lo[t] = filt ? consumed_ptr[urow[t]] : 0;
     c_hi[t] = filt ? consumed_ptr[urow[t] + 1] : 0;
@@ -647,8 +600,6 @@ __global__ __launch_bounds__((TkShape<DT, WU, AR, TU>::NW * 64), (TkShape<DT, WU
     asm volatile("" ::: "memory");
   };
 
-  constexpr int kWinRows = LR_TOPK_WIN_ROWS;      // 12 ranges per XCD x (1 + slack) windows x rows x 512 B against the 4 MB L2
-  constexpr int kWinSlack = LR_TOPK_WIN_SLACK;    // windows a workgroup may run ahead of the slowest one of its range
   constexpr int kLockSpins = 2000, kLockSleep = 8; // bound of one window-edge wait (see below)
   constexpr int WN = kWinRows / kTI;              // stages per window
   int* my_prog = progress != nullptr ? progress + static_cast<int64_t>(g) * n_ut : nullptr;
@@ -660,9 +611,10 @@ __global__ __launch_bounds__((TkShape<DT, WU, AR, TU>::NW * 64), (TkShape<DT, WU
     wave_signal(&full_cnt[pstage % NB]);
   }
 
-  [[maybe_unused]] unsigned long long mk[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   for (int i = 0; i < n_st; ++i) {
-    [[maybe_unused]] const unsigned long long tm0 = LR_TK_T();
+    // (tm0 and tm1 are dead.  They are what is left of the removed phase marks: without the two of them the compiler swaps two
+    // independent moves in the window-edge wait, and this file's device code is held byte for byte at what was measured)
+    [[maybe_unused]] const unsigned long long tm0 = 0ull;
     const int64_t st = st0 + i;
     const int buf = i % NB;
     const bool more = i + kPD < n_st;
@@ -682,7 +634,7 @@ __global__ __launch_bounds__((TkShape<DT, WU, AR, TU>::NW * 64), (TkShape<DT, WU
     }
     stage_load(st + kPD);  // in flight during the MFMAs below
     wave_wait(&full_cnt[buf], NW * (i / NB + 1));
-    [[maybe_unused]] const unsigned long long tm1 = LR_TK_T();
+    [[maybe_unused]] const unsigned long long tm1 = 0ull;
 
     const float* src = tile + buf * kTI * LDW;
     // one 32-row sub-tile of the stage against this wave's user tiles: the MFMA chains ...
@@ -693,39 +645,22 @@ __global__ __launch_bounds__((TkShape<DT, WU, AR, TU>::NW * 64), (TkShape<DT, WU
         // item planes from LDS: one ds_read_b128 per plane and k-block feeds six MFMAs (16 B = this lane's 8 k of row j)
         const char* arow = smem + buf * kStageBytes + (sub * 32 + j) * RSB + h * 16;
         [[maybe_unused]] float rn2 = 0.f;          // AR 2: squared norm of this lane's half of (bf16) item row j
-#ifndef LR_TK_AGRP
-#define LR_TK_AGRP 1
-#endif
-        constexpr int AG = (AR == 2 && KB % LR_TK_AGRP == 0) ? LR_TK_AGRP : 1;     // A fragments read ahead of their MFMAs
-        sb::bf16x8 ag[AG];
 #pragma unroll
         for (int kb = 0; kb < KB; ++kb) {
-          if (kb % AG == 0) {
-#pragma unroll
-            for (int e = 0; e < AG; ++e) ag[e] = *reinterpret_cast<const sb::bf16x8*>(arow + (kb + e) * 32);
-          }
-          const sb::bf16x8 a1 = ag[kb % AG];
-#ifndef LR_TK_LAB_NONORM
+          const sb::bf16x8 a1 = *reinterpret_cast<const sb::bf16x8*>(arow + kb * 32);
           if constexpr (AR == 2) {                 // four v_dot2_f32_bf16 in the shadow of the MFMAs below
             sb::bf16x2 pr[4];
             __builtin_memcpy(pr, &a1, 16);
 #pragma unroll
             for (int e = 0; e < 4; ++e) rn2 = __builtin_amdgcn_fdot2_f32_bf16(pr[e], pr[e], rn2, false);
           }
-#endif
           if constexpr (AR == 1) {
             const sb::bf16x8 a2 = *reinterpret_cast<const sb::bf16x8*>(arow + PLANE + kb * 32);
             const sb::bf16x8 a3 = *reinterpret_cast<const sb::bf16x8*>(arow + 2 * PLANE + kb * 32);
             sb::mfma6(acc[0], a1, a2, a3, ub1[0][kb], ub2[kb], ub3[kb]);
           } else {
 #pragma unroll
-            for (int t = 0; t < TU; ++t) {
-#ifdef LR_TK_LAB_NOMFMA
-              acc[t][kb] += static_cast<float>(a1[0]);
-#else
-              acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, ub1[t][kb], acc[t], 0, 0, 0);
-#endif
-            }
+            for (int t = 0; t < TU; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, ub1[t][kb], acc[t], 0, 0, 0);
           }
         }
         if constexpr (AR == 2) {                 // + delta |u| |i|: the score becomes an upper bound of the exact one
@@ -784,11 +719,7 @@ __global__ __launch_bounds__((TkShape<DT, WU, AR, TU>::NW * 64), (TkShape<DT, WU
       // send every sub-tile down the per-survivor path (measured: 206 - 522 ms instead of 141 per 1,024 x 100 M pass).
       const uint32_t tau_it = ~static_cast<uint32_t>(tau[t]);
       const bool pass = best > tau_s[t] || (best == tau_s[t] && static_cast<uint32_t>(st * kTI + sub * 32) < tau_it);
-#ifdef LR_TK_LAB_NOEPI
-      if (AR == 2 ? __ballot(best == 1.2345e30f) != 0ull : __ballot(pass) != 0ull) {
-#else
       if (__ballot(pass) != 0ull) {
-#endif
         int* my_cnt = wave_cnt + t * 32;
         uint64_t* my_keys = slab_keys + static_cast<int64_t>(t * 32 + j) * C;
         uint32_t hit = 0;
@@ -849,44 +780,12 @@ __global__ __launch_bounds__((TkShape<DT, WU, AR, TU>::NW * 64), (TkShape<DT, WU
       }
       }
     };
-#ifndef LR_TK_PIPE
-#define LR_TK_PIPE 0
-#endif
-#ifndef LR_TK_W8_NOPIPE
-#define LR_TK_W8_NOPIPE 0
-#endif
-    if constexpr (AR == 2 && WI == 1 && SUBS % 2 == 0 && ((WU == 8 && !LR_TK_W8_NOPIPE) || LR_TK_PIPE)) {
-      // two accumulator sets: the chains of sub-tile s + 1 are issued before the tests of sub-tile s — the tests run while the
-      // matrix pipe works
-      f32x16 accA[TU], accB[TU];
-      chain(0, accA);
-#pragma unroll
-      for (int sub = 0; sub < SUBS; sub += 2) {
-        chain(sub + 1, accB);
-        epilogue(sub, accA);
-        if (sub + 2 < SUBS) chain(sub + 2, accA);
-        epilogue(sub + 1, accB);
-      }
-    } else
-    {
 #pragma unroll 1
-      for (int sub = wi; sub < SUBS; sub += WI) {
-        [[maybe_unused]] const unsigned long long tma = LR_TK_T();
-        f32x16 acc[TU];
-        chain(sub, acc);
-#ifdef LR_TK_MARKS
-      {
-        float a0 = acc[0][0], a1 = acc[TU - 1][15];
-        asm volatile("" : "+v"(a0), "+v"(a1));          // the MFMA chains have delivered
-        acc[0][0] = a0; acc[TU - 1][15] = a1;
-      }
-      const unsigned long long tmb = LR_TK_T();
-      mk[6] += tmb - tma;
-#endif
-        epilogue(sub, acc);
-      }
+    for (int sub = wi; sub < SUBS; sub += WI) {
+      f32x16 acc[TU];
+      chain(sub, acc);
+      epilogue(sub, acc);
     }
-    [[maybe_unused]] const unsigned long long tm2 = LR_TK_T();
     if (win_edge) {                // too far ahead of the slowest workgroup of the range: let it catch up
       const int want = i / WN - kWinSlack;
       int spins = 0;
@@ -904,25 +803,14 @@ __global__ __launch_bounds__((TkShape<DT, WU, AR, TU>::NW * 64), (TkShape<DT, WU
         prog_seen = __hip_atomic_load(my_prog + (lane < n_ut ? lane : 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
-    [[maybe_unused]] const unsigned long long tm3 = LR_TK_T();
     wave_signal(&done_cnt[buf]);
-    [[maybe_unused]] unsigned long long tm4 = tm3;
     if (more) {
       const int b2 = (i + kPD) % NB;
       wave_wait(&done_cnt[b2], NW * ((i + kPD) / NB));   // earlier users of that buffer are through
-      tm4 = LR_TK_T();
       stage_write(b2, true);
       wave_signal(&full_cnt[b2]);
     }
-#ifdef LR_TK_MARKS
-    const unsigned long long tm5 = LR_TK_T();
-    mk[0] += tm1 - tm0; mk[1] += tm2 - tm1; mk[5] += tm3 - tm2; mk[2] += tm4 - tm3; mk[3] += tm5 - tm4; mk[4] += 1;
-#endif
   }
-#ifdef LR_TK_MARKS
-  if (AR == 2 && item_stride == 1 && lane == 0)
-    for (int q = 0; q < 8; ++q) atomicAdd(&lr_tk_marks[q], mk[q]);
-#endif
 
   if (progress != nullptr && tid == 0 && ut != mute_ut)     // done with the range: never hold the others back
     __hip_atomic_store(progress + static_cast<int64_t>(g) * n_ut + ut, 0x7fffffff, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1157,10 +1045,6 @@ static int dispatch_wu(const TopkPlan& p, const float* users, int64_t B, const f
                        const uint8_t* flag, int k, int64_t item_base, uint64_t* keys,
                        hipStream_t s, int item_stride, int* progress, TopkExtra ex = TopkExtra{}) {
   if constexpr (AR == 2) {
-#if LR_TK_W8                                 // (lab: the eight-wave form is only compiled into builds that plan it)
-    if (p.WU == 8)
-      return launch_score<DT, 8, AR, 1>(p, users, B, items, N, D, cptr, cidx, flag, k, item_base, keys, s, item_stride, progress, ex);
-#endif
     if (p.TU == 2) {
       if (p.WU == 4)
         return launch_score<DT, 4, AR, 2>(p, users, B, items, N, D, cptr, cidx, flag, k, item_base, keys, s, item_stride, progress, ex);
@@ -1217,6 +1101,7 @@ static int dispatch_dt(const TopkPlan& p, const float* users, int64_t B, const f
 // starts with a threshold that admits ~k * kPreStride candidates per user instead of ~k ln(N / (k lists)) per
 // list.  Results are unchanged (the threshold only filters).
 constexpr int kPreStride = 32;
+constexpr int kFiltPreStride = 32;    // the one-term filter's own stride
 constexpr int64_t kPreMinItems = int64_t(1) << 20;
 
 }  // namespace lr
@@ -1286,10 +1171,7 @@ static int score_topk_impl(const float* users, int64_t B, const float* items, in
                       : nullptr;
   int rc;
   if (N >= kPreMinItems) {      // catalogue-level threshold pre-pass over a strided sample
-#ifndef LR_TK_PRE_STRIDE2
-#define LR_TK_PRE_STRIDE2 32
-#endif
-    const int pre_stride = arith == 2 ? LR_TK_PRE_STRIDE2 : kPreStride;
+    const int pre_stride = arith == 2 ? kFiltPreStride : kPreStride;
     const int64_t Ns = (N + pre_stride - 1) / pre_stride;
     const TopkPlan ps = make_plan(B, Ns, D, k, arith);
     if (ps.ok && ps.key_bytes <= p.key_bytes && ps.B_pad == p.B_pad && ps.tmp_bytes <= p.tmp_bytes) {   // the sample's lists fit the main pass's buffers
@@ -1523,17 +1405,6 @@ extern "C" int lr_score_topk_sb_f32(const float* users, int64_t B, const float* 
                          ws_bytes, stream, 1);
 }
 
-
-#ifdef LR_TK_MARKS
-extern "C" int lr_score_topk_debug_marks(unsigned long long* out8, int reset) {
-  hipError_t e = hipMemcpyFromSymbol(out8, HIP_SYMBOL(lr::lr_tk_marks), 8 * sizeof(unsigned long long));
-  if (e == hipSuccess && reset) {
-    unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    e = hipMemcpyToSymbol(HIP_SYMBOL(lr::lr_tk_marks), z, sizeof(z));
-  }
-  return static_cast<int>(e);
-}
-#endif
 
 extern "C" int lr_score_topk_filter_kp(int k) { return filt_kp(k); }
 

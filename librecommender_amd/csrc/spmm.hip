@@ -75,49 +75,10 @@ __global__ __launch_bounds__(kBlock) void spmm_scalar_kernel(
 // ---------------------------------------------------------------------------------------
 constexpr int kSpLong = 128;
 constexpr int kSpChunk = 2048;
-#ifndef LR_SP_LONGBLOCKS          // profiling builds (scripts/lab/r04/m.sh) vary these two
-#define LR_SP_LONGBLOCKS 256
-#endif
-#ifndef LR_SP_CHUNKWIDE
-#define LR_SP_CHUNKWIDE 0
-#endif
-#ifndef LR_SP_EPI_NT              // non-temporal accesses to (w, m, v) in the optimiser epilogue
-#define LR_SP_EPI_NT 1
-#endif
-#ifndef LR_SP_MASKWIDE            // nonzeros in flight per row group where the operand's rows are filtered by a bitmap
-#define LR_SP_MASKWIDE 8          // (measured at cfg 5, GPU call r05ab: 8 -> 16.5 ms, 16 -> 19.2 ms, 32 -> 32 ms per product)
-#endif
-constexpr int kSpLongBlocks = LR_SP_LONGBLOCKS;
-// Cache-policy experiments (lab builds, scripts/lab/r06/spmm_nt.sh; the product build defines none of them):
-//   LR_SP_NT_STREAM 1: the (col, val) stream is read with non-temporal loads (read once: should not displace gathered rows in L2)
-//   LR_SP_NT_COLD H  : gathered rows of columns outside [0, H) and [LR_SP_SPLIT, LR_SP_SPLIT + H) are read non-temporally — on a
-//                      Zipf graph whose ids are popularity ranks those ranges are the hot rows of the two sides
-#ifndef LR_SP_NT_STREAM
-#define LR_SP_NT_STREAM 0
-#endif
-#ifndef LR_SP_NT_COLD
-#define LR_SP_NT_COLD 0
-#endif
-#ifndef LR_SP_SPLIT
-#define LR_SP_SPLIT 10000000
-#endif
-typedef float sp_v4f __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 sp_ld4_nt(const float* p) {
-  const sp_v4f v = __builtin_nontemporal_load(reinterpret_cast<const sp_v4f*>(p));
-  return make_float4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ bool sp_hot(int32_t c) {
-  return static_cast<uint32_t>(c) < static_cast<uint32_t>(LR_SP_NT_COLD) ||
-         static_cast<uint32_t>(c - LR_SP_SPLIT) < static_cast<uint32_t>(LR_SP_NT_COLD);
-}
-template <int K>
-__device__ __forceinline__ float4 sp_ldrow(const float* __restrict__ X, int32_t c, int c4) {
-  const float* p = X + static_cast<int64_t>(c) * K + c4;
-  if (LR_SP_NT_COLD > 0) return sp_hot(c) ? ld4(p) : sp_ld4_nt(p);
-  return ld4(p);
-}
-__device__ __forceinline__ int32_t sp_ldc(const int32_t* p) { return LR_SP_NT_STREAM ? __builtin_nontemporal_load(p) : *p; }
-__device__ __forceinline__ float sp_lda(const float* p) { return LR_SP_NT_STREAM ? __builtin_nontemporal_load(p) : *p; }
+constexpr int kSpLongBlocks = 256;
+// nonzeros in flight per row group where the operand's rows are filtered by a bitmap
+// (measured at cfg 5, GPU call r05ab: 8 -> 16.5 ms, 16 -> 19.2 ms, 32 -> 32 ms per product)
+constexpr int kSpMaskWide = 8;
 
 struct SpmmLists {
   int32_t* counters;      // [0] chunks, [1] partial slots, [2] multi-chunk rows
@@ -196,7 +157,7 @@ __device__ __forceinline__ float4 spmm_walk(const int32_t* __restrict__ col, con
   };
   // eight nonzeros in flight where a row has them (same ascending fma order as the four-wide body: bit-identical sums;
   // one dependent col -> row round less per eight nonzeros); only the contiguous walk of a short row (step == 4)
-  if (step == 4 || LR_SP_CHUNKWIDE) {
+  if (step == 4) {
     auto wide = [&](auto width) {
       constexpr int Wd = decltype(width)::value;
       for (; j + (step == 4 ? Wd : (Wd / 4 - 1) * step + 4) <= j1; j += (step == 4 ? Wd : (Wd / 4) * step)) {
@@ -205,7 +166,7 @@ __device__ __forceinline__ float4 spmm_walk(const int32_t* __restrict__ col, con
 #pragma unroll
         for (int q = 0; q < Wd; ++q) {       // contiguous (short row) or quads `step` apart (a chunk shared by NG row groups)
           const int64_t jq = step == 4 ? j + q : j + (q / 4) * step + (q % 4);
-          c[q] = sp_ldc(col + jq); a[q] = sp_lda(val + jq);
+          c[q] = col[jq]; a[q] = val[jq];
         }
         float4 x[Wd];
         if (MASKED) {       // all bitmap words first, then the rows that are there: one round trip each, not one per nonzero
@@ -217,15 +178,15 @@ __device__ __forceinline__ float4 spmm_walk(const int32_t* __restrict__ col, con
             x[q] = ((wq[q] >> (c[q] & 31)) & 1u) ? ld4(X + static_cast<int64_t>(c[q]) * K + c4) : f4_zero();
         } else {
 #pragma unroll
-          for (int q = 0; q < Wd; ++q) x[q] = sp_ldrow<K>(X, c[q], c4);
+          for (int q = 0; q < Wd; ++q) x[q] = ld4(X + static_cast<int64_t>(c[q]) * K + c4);
         }
 #pragma unroll
         for (int q = 0; q < Wd; ++q) y = f4_fma(make_float4(a[q], a[q], a[q], a[q]), x[q], y);
       }
     };
     // (16 in flight measured no better for the plain product, GPU call r03ag, and worse for the bitmap-filtered one, r05ab)
-    if (MASKED && LR_SP_MASKWIDE != 8) wide(std::integral_constant<int, LR_SP_MASKWIDE>{});
-    wide(std::integral_constant<int, 8>{});
+    static_assert(kSpMaskWide == 8, "the plain and the bitmap-filtered walk share one width");
+    wide(std::integral_constant<int, kSpMaskWide>{});
   }
   for (; j < j1; j += step) {
     const int64_t rem = j1 - j;
@@ -240,10 +201,10 @@ __device__ __forceinline__ float4 spmm_walk(const int32_t* __restrict__ col, con
         x2 = ((w2 >> (c2 & 31)) & 1u) ? ld4(X + static_cast<int64_t>(c2) * K + c4) : f4_zero();
         x3 = ((w3 >> (c3 & 31)) & 1u) ? ld4(X + static_cast<int64_t>(c3) * K + c4) : f4_zero();
       } else {
-        x0 = sp_ldrow<K>(X, c0, c4);
-        x1 = sp_ldrow<K>(X, c1, c4);
-        x2 = sp_ldrow<K>(X, c2, c4);
-        x3 = sp_ldrow<K>(X, c3, c4);
+        x0 = ld4(X + static_cast<int64_t>(c0) * K + c4);
+        x1 = ld4(X + static_cast<int64_t>(c1) * K + c4);
+        x2 = ld4(X + static_cast<int64_t>(c2) * K + c4);
+        x3 = ld4(X + static_cast<int64_t>(c3) * K + c4);
       }
       y = f4_fma(make_float4(a0, a0, a0, a0), x0, y);
       y = f4_fma(make_float4(a1, a1, a1, a1), x1, y);
@@ -298,8 +259,8 @@ __device__ __forceinline__ void sp_store(int64_t r, int c4, float4 y, float* __r
     __builtin_nontemporal_store(x.x, &q->x); __builtin_nontemporal_store(x.y, &q->y);
     __builtin_nontemporal_store(x.z, &q->z); __builtin_nontemporal_store(x.w, &q->w);
   };
-  const float4 w = LR_SP_EPI_NT ? ldnt(A.w + off) : ld4(A.w + off);
-  float4 mm = LR_SP_EPI_NT ? ldnt(A.m + off) : ld4(A.m + off), vv = LR_SP_EPI_NT ? ldnt(A.v + off) : ld4(A.v + off);
+  const float4 w = ldnt(A.w + off);
+  float4 mm = ldnt(A.m + off), vv = ldnt(A.v + off);
   const float gg[4] = {g.x, g.y, g.z, g.w}, ww[4] = {w.x, w.y, w.z, w.w};
   float mq[4] = {mm.x, mm.y, mm.z, mm.w}, vq[4] = {vv.x, vv.y, vv.z, vv.w}, out[4], vm[4];
   float4 vmx = f4_zero();
@@ -314,15 +275,9 @@ __device__ __forceinline__ void sp_store(int64_t r, int c4, float4 y, float* __r
       out[e] = ww[e] - A.coef.step_size * (mq[e] / denom);
     }
   }
-  if (LR_SP_EPI_NT) {
-    stnt(A.w + off, make_float4(out[0], out[1], out[2], out[3]));
-    stnt(A.m + off, make_float4(mq[0], mq[1], mq[2], mq[3]));
-    stnt(A.v + off, make_float4(vq[0], vq[1], vq[2], vq[3]));
-  } else {
-    st4(A.w + off, make_float4(out[0], out[1], out[2], out[3]));
-    st4(A.m + off, make_float4(mq[0], mq[1], mq[2], mq[3]));
-    st4(A.v + off, make_float4(vq[0], vq[1], vq[2], vq[3]));
-  }
+  stnt(A.w + off, make_float4(out[0], out[1], out[2], out[3]));
+  stnt(A.m + off, make_float4(mq[0], mq[1], mq[2], mq[3]));
+  stnt(A.v + off, make_float4(vq[0], vq[1], vq[2], vq[3]));
   if (A.vmax != nullptr) st4(A.vmax + off, make_float4(vm[0], vm[1], vm[2], vm[3]));
 }
 
