@@ -1095,6 +1095,39 @@ int lr_rnn_layer_bwd_f32(int cell, int act, const float* x, const float* table, 
                          const float* ghs, float* gx, float* gW, float* gU, float* gb, void* ws, size_t ws_bytes,
                          lr_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * WaveNet — the user side of libreco/algorithms/wave_net.py:181-222 (TF2 branch) in one forward launch: n_blocks *
+ * n_per_block dilated causal convolutions of kernel size 2 with ReLU, a 1x1 convolution with ReLU and a max pool over time,
+ * f32 on the VALU.  L, D (table width) and F (filters) in [1, 128], at most 16 dilated layers (lr_wavenet_supported, otherwise
+ * LR_ESHAPE).  No float atomics anywhere: same bits from run to run.
+ *   a_0[b, t] = table[ids[b, t]] (table [V, D], ids int32 [B, L], read in place; an id outside [0, V) is never dereferenced:
+ *   a zero input row, gx exactly 0).  There is no sequence mask: pad positions take part like any other.
+ *   layer j < n_layers:  a_{j+1}[t] = relu(bias_j + a_j[t - d_j] K_j[0] + a_j[t] K_j[1]), d_j = 2^(j mod n_per_block),
+ *                        a_j[t - d_j] = 0 for t < d_j (Keras padding="causal"; tap 0 is the earlier step); K_j [2, C_j, F],
+ *                        C_0 = D, C_j = F after that
+ *   layer n_layers:      relu(bias + a K), K [1, F, F]
+ *   pooled[b, f] = max_t of the last layer, arg[b, f] = the smallest t that attains it.  ReLU's derivative at 0 is 0.
+ * Parameter layout (the contract; it is how layers/dense.py `DenseParams` lays out tensors added in this order): one f32
+ * buffer holding, for j = 0 .. n_layers, K_j (row-major [taps, C_j, F]) then bias_j [F], every tensor starting on a 16-byte
+ * boundary (its length rounded up to 4 floats; the gap is not read).  lr_wavenet_params_bytes is the buffer's length.
+ * `gparams` has the same layout; the backward writes every element of it (the gaps as 0).
+ *   forward   writes every element of acts (lr_wavenet_fwd_acts_bytes: [n_layers + 1, B, L, F] row-major, slab j = the post-ReLU
+ *             output of layer j), pooled [B, F] and arg int32 [B, F].
+ *   backward  from gpooled [B, F]: writes every element of gx [B, L, D] and gparams.  The ReLU pattern is acts > 0.  Weight and
+ *             bias gradients are summed over B L as per-chunk partials in `ws` (lr_wavenet_bwd_ws_bytes bytes, contents
+ *             arbitrary on entry) added in chunk order.
+ * ---------------------------------------------------------------------------------- */
+int lr_wavenet_supported(int L, int D, int F, int n_blocks, int n_per_block);
+size_t lr_wavenet_params_bytes(int D, int F, int n_blocks, int n_per_block);
+size_t lr_wavenet_fwd_acts_bytes(int64_t B, int L, int F, int n_blocks, int n_per_block);
+size_t lr_wavenet_bwd_ws_bytes(int64_t B, int L, int D, int F, int n_blocks, int n_per_block);
+int lr_wavenet_fwd_f32(const float* table, int64_t V, const int32_t* ids, int64_t B, int L, int D, int F, int n_blocks,
+                       int n_per_block, const float* params, float* acts, size_t acts_bytes, float* pooled, int32_t* arg,
+                       lr_stream_t stream);
+int lr_wavenet_bwd_f32(const float* table, int64_t V, const int32_t* ids, int64_t B, int L, int D, int F, int n_blocks,
+                       int n_per_block, const float* params, const float* acts, const float* gpooled, const int32_t* arg,
+                       float* gx, float* gparams, void* ws, size_t ws_bytes, lr_stream_t stream);
+
 /* Measurement probe (scripts/mfma_peak.py): iters x 8 back-to-back v_mfma_f32_32x32x2_f32 per wave on
  * 256 x waves_per_simd workgroups — the f32 MFMA rate the chip sustains at the clock it holds under that load. */
 int lr_mfma_f32_probe(int iters, int waves_per_simd, float* out, lr_stream_t stream);

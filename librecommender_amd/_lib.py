@@ -235,6 +235,12 @@ SIGNATURES = {
                                     _p]),
     "lr_rnn_layer_bwd_f32": (_int, [_int, _int, _p, _p, _i64, _p, _p, _i64, _int, _int, _int, _p, _p, _p, _p, _p, _p, _p, _p,
                                     _p, _p, _p, _p, _sz, _p]),
+    "lr_wavenet_supported": (_int, [_int, _int, _int, _int, _int]),
+    "lr_wavenet_params_bytes": (_sz, [_int, _int, _int, _int]),
+    "lr_wavenet_fwd_acts_bytes": (_sz, [_i64, _int, _int, _int, _int]),
+    "lr_wavenet_bwd_ws_bytes": (_sz, [_i64, _int, _int, _int, _int, _int]),
+    "lr_wavenet_fwd_f32": (_int, [_p, _i64, _p, _i64, _int, _int, _int, _int, _int, _p, _p, _sz, _p, _p, _p]),
+    "lr_wavenet_bwd_f32": (_int, [_p, _i64, _p, _i64, _int, _int, _int, _int, _int, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
 }
 
 _lib = None

@@ -13,7 +13,8 @@ from .swing import Swing
 from .transformer import Transformer
 from .two_tower import TwoTower
 from .user_cf import UserCF
+from .wavenet import WaveNet
 from .youtube_ranking import YouTubeRanking
 from .youtube_retrieval import YouTubeRetrieval
 
-__all__ = ["ALS", "BPR", "DIN", "DeepFM", "FM", "ItemCF", "LightGCN", "NGCF", "RNN4Rec", "SIM", "SVD", "SVDpp", "Swing", "Transformer", "TwoTower", "UserCF", "YouTubeRanking", "YouTubeRetrieval"]
+__all__ = ["ALS", "BPR", "DIN", "DeepFM", "FM", "ItemCF", "LightGCN", "NGCF", "RNN4Rec", "SIM", "SVD", "SVDpp", "Swing", "Transformer", "TwoTower", "UserCF", "WaveNet", "YouTubeRanking", "YouTubeRetrieval"]

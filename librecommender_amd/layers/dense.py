@@ -47,7 +47,10 @@ class DenseParams:
             n = math.prod(shape)
             p = self.flat[off:off + n].view(shape)
             if init == "glorot_uniform":
-                fan_in, fan_out = (shape[0], shape[1]) if len(shape) == 2 else (shape[0], shape[0])
+                if len(shape) == 3:             # a Keras Conv1D kernel [k, C_in, C_out]: the receptive field scales both fans
+                    fan_in, fan_out = shape[0] * shape[1], shape[0] * shape[2]
+                else:
+                    fan_in, fan_out = (shape[0], shape[1]) if len(shape) == 2 else (shape[0], shape[0])
                 limit = math.sqrt(6.0 / (fan_in + fan_out))
                 p.uniform_(-limit, limit, generator=self.gen)
             elif init == "ones":

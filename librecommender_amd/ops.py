@@ -2159,3 +2159,71 @@ def rnn_layer_bwd(cell: str, W: torch.Tensor, U: torch.Tensor, lens: torch.Tenso
           _ptr(in_mask), _ptr(rec_mask), _ptr(hs), _ptr(saved), _ptr(ghs), _ptr(gx), _ptr(gW), _ptr(gU), _ptr(gb), _ptr(ws),
           ws.numel(), _stream())
     return gx, gW, gU, gb
+
+
+# --------------------------------------------------------------------------------------
+# WaveNet stack (csrc/wavenet.hip)
+# --------------------------------------------------------------------------------------
+def wavenet_supported(L: int, D: int, F: int, n_blocks: int, n_per_block: int) -> bool:
+    """Whether the WaveNet kernels take windows of `L` ids, a table of width `D`, `F` filters and this many layers."""
+    return bool(_lib.load().lr_wavenet_supported(int(L), int(D), int(F), int(n_blocks), int(n_per_block)))
+
+
+def wavenet_param_floats(D: int, F: int, n_blocks: int, n_per_block: int) -> int:
+    """Length of the parameter buffer (conv1d/kernel, conv1d/bias, conv1d_1/kernel, ... then the 1x1 pair, every tensor on a
+    16-byte boundary: the layout `DenseParams` gives tensors added in that order); 0 for an unsupported shape."""
+    return _lib.load().lr_wavenet_params_bytes(int(D), int(F), int(n_blocks), int(n_per_block)) // 4
+
+
+def _wavenet_check(table, ids, params, F, n_blocks, n_per_block):
+    """-> (B, L, D, V) of one WaveNet call, its operands validated."""
+    D = _req(table, torch.float32, "table", 2).shape[1]
+    _req(ids, torch.int32, "ids", 2)
+    _req(params, torch.float32, "params", 1)
+    B, L = ids.shape
+    if table.shape[0] < 1:
+        raise ValueError("table must hold at least one row")
+    if not wavenet_supported(L, D, F, n_blocks, n_per_block):
+        raise ValueError(f"unsupported WaveNet shape: L={L}, D={D}, F={F}, {n_blocks} x {n_per_block} layers (L, D and F from 1 "
+                         "to 128, at most 16 dilated layers)")
+    if params.numel() != wavenet_param_floats(D, F, n_blocks, n_per_block):
+        raise ValueError("params must be the flat parameter buffer of this shape (see `wavenet_param_floats`)")
+    if params.data_ptr() % 16:
+        raise ValueError("params must start on a 16-byte boundary")
+    return B, L, D, table.shape[0]
+
+
+def wavenet_fwd(table: torch.Tensor, ids: torch.Tensor, params: torch.Tensor, F: int, n_blocks: int, n_per_block: int):
+    """`lr_wavenet_fwd_f32`: the dilated stack, the 1x1 layer and the pool over the rows table[ids] read in place.  Returns
+    (acts [n_layers + 1, B, L, F], pooled [B, F], arg int32 [B, F])."""
+    B, L, D, V = _wavenet_check(table, ids, params, F, n_blocks, n_per_block)
+    nl, dev = n_blocks * n_per_block, table.device
+    acts = torch.empty((nl + 1, max(B, 1), L, F), dtype=torch.float32, device=dev)[:, :B]
+    pooled = torch.empty((max(B, 1), F), dtype=torch.float32, device=dev)[:B]
+    arg = torch.empty((max(B, 1), F), dtype=torch.int32, device=dev)[:B]
+    if B == 0:
+        return acts, pooled, arg
+    _call("lr_wavenet_fwd_f32", _ptr(table), V, _ptr(ids), B, L, D, F, n_blocks, n_per_block, _ptr(params), _ptr(acts),
+          acts.numel() * 4, _ptr(pooled), _ptr(arg), _stream())
+    return acts, pooled, arg
+
+
+def wavenet_bwd(table: torch.Tensor, ids: torch.Tensor, params: torch.Tensor, F: int, n_blocks: int, n_per_block: int,
+                acts: torch.Tensor, arg: torch.Tensor, gpooled: torch.Tensor, gparams: Optional[torch.Tensor] = None):
+    """`lr_wavenet_bwd_f32`: from gpooled [B, F] -> (gx [B, L, D], gparams in the layout of `params`); `gparams` may be given
+    (e.g. a slice of `DenseParams.grad`) and is overwritten.  Parameter gradients are summed in a fixed order."""
+    B, L, D, V = _wavenet_check(table, ids, params, F, n_blocks, n_per_block)
+    nl, dev = n_blocks * n_per_block, table.device
+    if _req(acts, torch.float32, "acts", 4).shape != (nl + 1, B, L, F):
+        raise ValueError("acts must be the forward's [n_layers + 1, B, L, F]")
+    if _req(arg, torch.int32, "arg", 2).shape != (B, F) or _req(gpooled, torch.float32, "gpooled", 2).shape != (B, F):
+        raise ValueError("arg and gpooled must be [B, F]")
+    if gparams is None:
+        gparams = torch.empty_like(params)
+    elif _req(gparams, torch.float32, "gparams", 1).numel() != params.numel():
+        raise ValueError("gparams must have the length of params")
+    gx = torch.empty((max(B, 1), L, D), dtype=torch.float32, device=dev)[:B]
+    ws = torch.empty(max(_lib.load().lr_wavenet_bwd_ws_bytes(B, L, D, F, n_blocks, n_per_block), 256), dtype=torch.uint8, device=dev)
+    _call("lr_wavenet_bwd_f32", _ptr(table), V, _ptr(ids), B, L, D, F, n_blocks, n_per_block, _ptr(params), _ptr(acts),
+          _ptr(gpooled), _ptr(arg), _ptr(gx), _ptr(gparams), _ptr(ws), ws.numel(), _stream())
+    return gx, gparams
