@@ -1,7 +1,8 @@
 """`RNN4Rec` (`libreco/algorithms/rnn4rec.py`): the session-based recommender of Hidasi et al. (GRU4Rec; an LSTM is also
 offered), with the reference's constructor, checks, `fit / predict / recommend_user / dyn_user_embedding` and checkpoints.
 The recurrent layers run on csrc/rnn.hip (one forward and one backward call per layer, `nets/rnn_nets.py`), the exported
-embeddings are served by `lr_score_topk_f32` like every `EmbedBase` model.
+embeddings are served by `lr_score_topk_f32` like every `EmbedBase` model.  Dynamic inference (`recommend_user` with a `seq`,
+the window) is `bases/dyn_embed_base.py`'s, the checkpoint arrays are its `SeqTowerCheckpoint`'s.
 
 Deliberate differences from the reference:
   (a) the arithmetic is the reference's TF2 branch (Keras `GRU` / `LSTM` under a sequence mask); its TF1 branch
@@ -16,21 +17,20 @@ Deliberate differences from the reference:
 from __future__ import annotations
 
 import numpy as np
-import torch
 
 from .. import ops
-from ..bases import EmbedBase
+from ..bases import DynEmbedBase
 from ..bases.base import hip_device
+from ..bases.dyn_embed_base import SeqTowerCheckpoint
 from ..batch.sequence import get_recent_seqs
 from ..layers.row_adam import REG_NEEDS_DENSE
 from ..nets.rnn_nets import RNN4RecNet
 from ..utils.validate import check_seq_mode, dropout_config, hidden_units_config, reg_config
 
-TABLES = ("seq_embeds_var", "item_embeds_var", "item_bias_var")
 
-
-class RNN4Rec(EmbedBase):
+class RNN4Rec(SeqTowerCheckpoint, DynEmbedBase):
     uses_sequence = True
+    takes_user_feats = False
 
     def __init__(self, task, data_info=None, loss_type="cross_entropy", rnn_type="gru", embed_size=16, norm_embed=False,
                  n_epochs=20, lr=0.001, lr_decay=False, epsilon=1e-5, reg=None, batch_size=256, sampler="random", num_neg=1,
@@ -78,103 +78,33 @@ class RNN4Rec(EmbedBase):
             return self.net.train_step(s.interacted_seq, s.interacted_len, pos=b.item_pairs[0], neg=b.item_pairs[1])
         return self.net.train_step(s.interacted_seq, s.interacted_len, items=b.items, labels=b.labels)
 
-    # ---- embeddings (`bases/dyn_embed_base.py:240-269`) ------------------------------------------
+    # ---- embeddings and dynamic inference --------------------------------------------------------
     def set_embeddings(self):
-        """Users: the net on the cached recent windows, a column of ones appended (the item side carries
-        `item_bias_var` there); items: `item_embeds_var` rows + the bias column."""
-        ue = self.net.embed_users(self.recent_seqs[: self.n_users], self.recent_seq_lens[: self.n_users])
-        w, bias = self.net.item_matrix()
-        self.user_embeds = torch.cat([ue, torch.ones_like(ue[:, :1])], dim=1).contiguous()
-        self.item_embeds = torch.cat([w, bias.view(-1, 1)], dim=1).contiguous()
+        """Users: the net on the cached recent windows."""
+        self._export_with_bias(self.net.embed_users(self.recent_seqs[: self.n_users], self.recent_seq_lens[: self.n_users]))
 
-    def convert_array_id(self, user, inner_id):
-        assert np.isscalar(user), f"User to convert must be scalar, got: {user}"
-        if inner_id:
-            if not isinstance(user, (int, np.integer)):
-                raise ValueError(f"`inner id` user must be int, got {user}")
-            return np.array([user if 0 <= user < self.n_users else self.n_users])
-        return np.array([self.data_info.user2id.get(user, self.n_users)])
+    def _default_window(self, uid):
+        return self.recent_seqs[[uid]]
 
-    def _window(self, uid, seq, inner_id):
-        """([1, L] window, [1] length) (`recommendation/preprocess.py:7-23,79-85`): the last L entries of `seq` (unknown
-        items become the pad id) or the user's cached recent window; no history is the one-step sequence [pad]."""
-        L, N = self.max_seq_len, self.n_items
+    def _window_len(self, uid, seq):
+        """[1] steps of the window `_window` builds: those of `seq` that fit, or the cached length; no history is the one-step
+        sequence [pad]."""
         if seq is None or len(seq) == 0:
-            return self.recent_seqs[[uid]], self.recent_seq_lens[[uid]]
-        ids = list(seq) if inner_id else [self.data_info.item2id.get(i, N) for i in seq]
-        ids = [i if 0 <= i < N else N for i in ids[-min(L, len(ids)):]]
-        out = np.full((1, L), N, dtype=np.int32)
-        out[0, : len(ids)] = ids
-        return out, np.array([max(len(ids), 1)], dtype=np.int32)
+            return self.recent_seq_lens[[uid]]
+        return np.array([max(min(len(seq), self.max_seq_len), 1)], dtype=np.int32)
 
     def dyn_user_embedding(self, user, user_feats=None, seq=None, include_bias=False, inner_id=False):
-        from ..recommendation import check_dynamic_rec_feats
-
-        if user_feats is not None:
-            raise ValueError("`RNN4Rec` has no user features: `user_feats` is not supported")
-        check_dynamic_rec_feats(self.model_name, user, user_feats, seq)
+        self._check_dynamic(user, user_feats, seq)
         uid = int(self.convert_array_id(user, inner_id)[0])
-        vec = self.net.embed_users(*self._window(uid, seq, inner_id))[0].cpu().numpy()
+        vec = self.net.embed_users(self._window(uid, seq, inner_id), self._window_len(uid, seq))[0].cpu().numpy()
         return np.append(vec, np.float32(1.0)) if include_bias else vec
 
-    def recommend_user(self, user, n_rec, user_feats=None, seq=None, cold_start="average", inner_id=False,
-                       filter_consumed=True, random_rec=False):
-        if user_feats is not None:
-            raise ValueError("`RNN4Rec` has no user features: `user_feats` is not supported")
-        if seq is None:
-            return super().recommend_user(user, n_rec, cold_start, inner_id, filter_consumed, random_rec)
-        from ..recommendation import check_dynamic_rec_feats, recommend_from_embedding
-
-        check_dynamic_rec_feats(self.model_name, user, user_feats, seq)
-        vec = torch.from_numpy(self.dyn_user_embedding(user, None, seq, include_bias=True, inner_id=inner_id)).view(1, -1)
-        uid = int(self.convert_array_id(user, inner_id)[0])
-        recs = recommend_from_embedding(self, [uid], n_rec, None, self.item_embeds, filter_consumed, random_rec,
-                                        user_vectors=vec)[0]
-        return {user: recs if inner_id else np.array([self.data_info.id2item[i] for i in recs.tolist()])}
-
     # ---- persistence ----------------------------------------------------------------------------
-    def variables_np(self):
-        out = {}
-        for k, v in self.net.vars.items():
-            out[f"embedding/{k}"] = (v.view(-1) if k == "item_bias_var" else v).cpu().numpy()
-        out.update({k: p.detach().cpu().numpy() for k, p in self.net.P.params.items()})
-        return out
-
-    def optimizer_arrays(self):
-        P = self.net.P
-        return {**self.net.optimizer_arrays(), "opt::dense_m": P.m.cpu().numpy(), "opt::dense_v": P.v.cpu().numpy()}
-
-    def load_variables_np(self, arrays):
-        with torch.no_grad():
-            for k, var in self.net.vars.items():
-                if f"embedding/{k}" in arrays:
-                    var.copy_(torch.from_numpy(arrays[f"embedding/{k}"]).view_as(var))
-            for k, p in self.net.P.params.items():
-                if k in arrays:
-                    p.copy_(torch.from_numpy(arrays[k]))
-
     def rebuild_model(self, path, model_name, full_assign=True):
         """Retraining on merged data: items keep their ids (new ones are appended), so the first `n_items` rows of the three
         tables are the saved ones; the pad row of `seq_embeds_var` moves from the old `n_items` to the new one; recurrent,
         layer-norm and Dense parameters have the same shapes and are copied.  With `full_assign` the Adam moments follow
         and the step count is restored."""
         arrays, old = self._begin_rebuild(path, model_name)
-        net, n_old = self.net, int(old.n_items)
-        net.take_over(arrays, lambda k: f"embedding/{k}", lambda k: n_old, full_assign)
-        with torch.no_grad():
-            pad_sets = [(net.vars["seq_embeds_var"], "embedding/seq_embeds_var")]
-            if full_assign:
-                pad_sets += [(net.m["seq_embeds_var"], "opt::m_seq_embeds_var"), (net.v["seq_embeds_var"], "opt::v_seq_embeds_var")]
-            for dst, key in pad_sets:
-                if key in arrays:
-                    dst[self.n_items] = torch.from_numpy(arrays[key][n_old]).to(dst.device)
-            P = net.P
-            same = all(k in arrays and tuple(arrays[k].shape) == tuple(p.shape) for k, p in P.params.items())
-            for k, p in P.params.items():
-                if k in arrays and tuple(arrays[k].shape) == tuple(p.shape):
-                    p.copy_(torch.from_numpy(arrays[k]))
-                else:
-                    print(f'variable "{k}" is not in the saved model or changed its shape, will be skipped.')
-            if full_assign and same and "opt::dense_m" in arrays and arrays["opt::dense_m"].shape == tuple(P.m.shape):
-                P.m.copy_(torch.from_numpy(arrays["opt::dense_m"]))
-                P.v.copy_(torch.from_numpy(arrays["opt::dense_v"]))
+        n_old = int(old.n_items)
+        self._take_over(arrays, dict.fromkeys(self.net.vars, n_old), {"seq_embeds_var": (n_old, self.n_items)}, full_assign)

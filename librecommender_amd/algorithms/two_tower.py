@@ -1,18 +1,19 @@
 """`TwoTower` (`libreco/algorithms/two_tower.py`): same constructor, same errors, same
-`fit / predict / recommend_user`, on the MI355X hot path."""
+`fit / predict / recommend_user`, on the MI355X hot path.  The id conversion, the dynamic branch of `recommend_user` and the
+user-feature override are `bases/dyn_embed_base.py`'s."""
 from __future__ import annotations
 
 import numpy as np
 import torch
 
-from ..bases import EmbedBase
+from ..bases import DynEmbedBase
 from ..bases.base import hip_device
 from ..batch.batch_unit import PairwiseBatch
 from ..nets import TwoTowerNet
 from ..utils.validate import dropout_config, hidden_units_config, reg_config, sparse_feat_size
 
 
-class TwoTower(EmbedBase):
+class TwoTower(DynEmbedBase):
     uses_features = True
 
     def __init__(self, task, data_info=None, loss_type="softmax", embed_size=16, norm_embed=False,
@@ -293,50 +294,13 @@ class TwoTower(EmbedBase):
         self.item_embeds = D.ShardedItemEmbeds(ie_loc, self.n_items, base, max(0, min(per, self.n_items - base)), net.group,
                                                net.kern)
 
-    # ---- dynamic inference (`bases/dyn_embed_base.py:74-238`) -------------------------------------
-    def convert_array_id(self, user, inner_id):
-        """One raw (or inner) user id -> `[inner id]`; unknown users map to the OOV id
-        (`bases/dyn_embed_base.py:60-72`)."""
-        assert np.isscalar(user), f"User to convert must be scalar, got: {user}"
-        if inner_id:
-            if not isinstance(user, (int, np.integer)):
-                raise ValueError(f"`inner id` user must be int, got {user}")
-            return np.array([user if 0 <= user < self.n_users else self.n_users])
-        return np.array([self.data_info.user2id.get(user, self.n_users)])
-
+    # ---- dynamic inference: `recommend_user` with `user_feats` is `DynEmbedBase`'s -------------------
     def dyn_user_embedding(self, user, user_feats=None, seq=None, include_bias=False, inner_id=False):
-        """User-tower output for ONE user with optional feature overrides (numpy, like the reference)."""
-        from ..feature_override import override_dense, override_sparse
-        from ..recommendation import check_dynamic_rec_feats
-
-        check_dynamic_rec_feats(self.model_name, user, user_feats, seq)
-        d = self.data_info
+        """User-tower output for ONE user with optional feature overrides (numpy, like the reference); there is no bias
+        column: `include_bias` changes nothing."""
+        self._check_dynamic(user, user_feats, seq)
         uid = int(self.convert_array_id(user, inner_id)[0])
-        if not 0 <= uid <= self.n_users:
-            uid = self.n_users
-        sp = de = None
-        if d.user_sparse_unique is not None:
-            sp = d.user_sparse_unique[[uid]]
-            if user_feats:
-                sp = override_sparse(d, sp, user_feats, d.user_sparse_col.name)
-        if d.user_dense_unique is not None:
-            de = d.user_dense_unique[[uid]]
-            if user_feats:
-                de = override_dense(d, de, user_feats, d.user_dense_col.name)
-        return self.net.embed_users(np.asarray([uid]), sp, de)[0].cpu().numpy()
-
-    def recommend_user(self, user, n_rec, user_feats=None, seq=None, cold_start="average",
-                       inner_id=False, filter_consumed=True, random_rec=False):
-        if user_feats is None and seq is None:
-            return super().recommend_user(user, n_rec, cold_start, inner_id, filter_consumed, random_rec)
-        from ..recommendation import check_dynamic_rec_feats, recommend_from_embedding
-
-        check_dynamic_rec_feats(self.model_name, user, user_feats, seq)
-        vec = torch.from_numpy(self.dyn_user_embedding(user, user_feats, seq, inner_id=inner_id)).view(1, -1)
-        uid = int(self.convert_array_id(user, inner_id)[0])
-        recs = recommend_from_embedding(self, [uid], n_rec, None, self.item_embeds, filter_consumed,
-                                        random_rec, user_vectors=vec)[0]
-        return {user: recs if inner_id else np.array([self.data_info.id2item[i] for i in recs.tolist()])}
+        return self.net.embed_users(np.asarray([uid]), *self._user_feature_rows(uid, user_feats))[0].cpu().numpy()
 
     def variables_np(self):
         t = self.net.tables
@@ -387,21 +351,12 @@ class TwoTower(EmbedBase):
                     off_new = {"user": t.user_off, "item": t.item_off, "sparse": t.sparse_off}[kind]
                     for name, new in (("opt::m", t.m), ("opt::v", t.v)):
                         new[torch.from_numpy(off_new + dst).to(dev)] = torch.from_numpy(arrays[name][off_old + src]).to(dev)
-            all_match = True
-            for k, p in P.params.items():
-                if k in arrays and tuple(arrays[k].shape) == tuple(p.shape):
-                    p.copy_(torch.from_numpy(arrays[k]))
-                else:
-                    all_match = False
-                    print(f'old and new shape of variable "{k}" doesn\'t match, will be skipped.')
+            P.take_over(arrays, full_assign)
             for k, bn in self._bn_layers().items():
                 if f"bn::{k}::mean" in arrays:
                     bn.moving_mean.copy_(torch.from_numpy(arrays[f"bn::{k}::mean"]))
                     bn.moving_var.copy_(torch.from_numpy(arrays[f"bn::{k}::var"]))
             if full_assign and "opt::step" in arrays:
-                if all_match and arrays["opt::dense_m"].shape == tuple(P.m.shape):
-                    P.m.copy_(torch.from_numpy(arrays["opt::dense_m"]))
-                    P.v.copy_(torch.from_numpy(arrays["opt::dense_v"]))
                 self.net.step = int(arrays["opt::step"])
 
     def load_variables_np(self, arrays):

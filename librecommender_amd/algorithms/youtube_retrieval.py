@@ -1,12 +1,14 @@
 """`YouTubeRetrieval` (`libreco/algorithms/youtube_retrieval.py`): same constructor, same errors, same
 `fit / predict / recommend_user / dyn_user_embedding`, on the MI355X path: history pooling through
-`lr_embed_bag_pool_f32`, the exported embeddings served by `lr_score_topk_f32` like every `EmbedBase` model."""
+`lr_embed_bag_pool_f32`, the exported embeddings served by `lr_score_topk_f32` like every `EmbedBase` model.  The id
+conversion, the dynamic branch of `recommend_user`, the window's tail and the user-feature override are
+`bases/dyn_embed_base.py`'s."""
 from __future__ import annotations
 
 import numpy as np
 import torch
 
-from ..bases import EmbedBase
+from ..bases import DynEmbedBase
 from ..bases.base import hip_device
 from ..batch.sequence import get_recent_seqs
 from ..nets import FeatSpec
@@ -15,7 +17,7 @@ from ..utils.validate import (check_multi_sparse, check_seq_mode, dropout_config
                               reg_config)
 
 
-class YouTubeRetrieval(EmbedBase):
+class YouTubeRetrieval(DynEmbedBase):
     uses_features = True
     uses_sequence = True
 
@@ -63,73 +65,23 @@ class YouTubeRetrieval(EmbedBase):
         self.apply_lr_schedule()
         return self.net.train_step(b.items, b.seqs.interacted_seq, b.sparse_indices, b.dense_values)
 
-    # ---- embeddings (`bases/dyn_embed_base.py:240-269`) ------------------------------------------
+    # ---- embeddings and dynamic inference --------------------------------------------------------
     def set_embeddings(self):
-        """Users: MLP output on the cached recent windows + stored user features, a column of ones appended
-        (the item side carries `item_bias_var` there); items: `item_embeds_var` rows (+ bias column)."""
+        """Users: MLP output on the cached recent windows + stored user features."""
         d = self.data_info
         us = d.user_sparse_unique[:-1] if d.user_sparse_unique is not None else None
         ud = d.user_dense_unique[:-1] if d.user_dense_unique is not None else None
-        ue = self.net.embed_users(self.recent_seqs[: self.n_users], us, ud)
-        w, bias = self.net.item_matrix()
-        self.user_embeds = torch.cat([ue, torch.ones_like(ue[:, :1])], dim=1).contiguous()
-        self.item_embeds = torch.cat([w, bias.view(-1, 1)], dim=1).contiguous()
+        self._export_with_bias(self.net.embed_users(self.recent_seqs[: self.n_users], us, ud))
 
-    def convert_array_id(self, user, inner_id):
-        assert np.isscalar(user), f"User to convert must be scalar, got: {user}"
-        if inner_id:
-            if not isinstance(user, (int, np.integer)):
-                raise ValueError(f"`inner id` user must be int, got {user}")
-            return np.array([user if 0 <= user < self.n_users else self.n_users])
-        return np.array([self.data_info.user2id.get(user, self.n_users)])
-
-    def _window(self, uid, seq, inner_id):
-        """[1, L] history window (`recommendation/preprocess.py:7-23,79-85`): the last L entries of `seq` (unknown
-        items pruned) or of the user's consumed list; the OOV user has no history."""
-        L, N = self.max_seq_len, self.n_items
-        if seq is not None and len(seq) > 0:
-            ids = list(seq) if inner_id else [self.data_info.item2id.get(i, N) for i in seq]
-        elif uid != self.n_users:
-            ids = list(self.user_consumed[uid])
-        else:
-            ids = []
-        ids = [i if 0 <= i < N else N for i in ids[-min(L, len(ids)):]] if ids else []
-        out = np.full((1, L), N, dtype=np.int32)
-        out[0, : len(ids)] = ids
-        return out
+    def _default_window(self, uid):
+        """The tail of the user's consumed list; the OOV user has no history."""
+        return self._pad_window(list(self.user_consumed[uid]) if uid != self.n_users else [])
 
     def dyn_user_embedding(self, user, user_feats=None, seq=None, include_bias=False, inner_id=False):
-        from ..feature_override import override_dense, override_sparse
-        from ..recommendation import check_dynamic_rec_feats
-
-        check_dynamic_rec_feats(self.model_name, user, user_feats, seq)
-        d = self.data_info
+        self._check_dynamic(user, user_feats, seq)
         uid = int(self.convert_array_id(user, inner_id)[0])
-        sp = de = None
-        if d.user_sparse_unique is not None:
-            sp = d.user_sparse_unique[[uid]]
-            if user_feats:
-                sp = override_sparse(d, sp, user_feats, d.user_sparse_col.name)
-        if d.user_dense_unique is not None:
-            de = d.user_dense_unique[[uid]]
-            if user_feats:
-                de = override_dense(d, de, user_feats, d.user_dense_col.name)
-        vec = self.net.embed_users(self._window(uid, seq, inner_id), sp, de)[0].cpu().numpy()
+        vec = self.net.embed_users(self._window(uid, seq, inner_id), *self._user_feature_rows(uid, user_feats))[0].cpu().numpy()
         return np.append(vec, np.float32(1.0)) if include_bias else vec
-
-    def recommend_user(self, user, n_rec, user_feats=None, seq=None, cold_start="average", inner_id=False,
-                       filter_consumed=True, random_rec=False):
-        if user_feats is None and seq is None:
-            return super().recommend_user(user, n_rec, cold_start, inner_id, filter_consumed, random_rec)
-        from ..recommendation import check_dynamic_rec_feats, recommend_from_embedding
-
-        check_dynamic_rec_feats(self.model_name, user, user_feats, seq)
-        vec = torch.from_numpy(self.dyn_user_embedding(user, user_feats, seq, include_bias=True,
-                                                       inner_id=inner_id)).view(1, -1)
-        uid = int(self.convert_array_id(user, inner_id)[0])
-        recs = recommend_from_embedding(self, [uid], n_rec, None, self.item_embeds, filter_consumed, random_rec,
-                                        user_vectors=vec)[0]
-        return {user: recs if inner_id else np.array([self.data_info.id2item[i] for i in recs.tolist()])}
 
     # ---- persistence ----------------------------------------------------------------------------
     def _bn_layers(self):

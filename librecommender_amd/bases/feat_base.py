@@ -299,22 +299,12 @@ class FeatBase(Base):
                 if new is None or key not in arrays:
                     continue
                 new[dst_t] = torch.from_numpy(arrays[key]).to(dev)[src_t]
-            all_match = True
-            for k, p in P.params.items():
-                a = arrays.get(f"dense::{k}")
-                if a is None or tuple(a.shape) != tuple(p.shape):
-                    all_match = False
-                    print(f'old and new shape of variable "{k}" doesn\'t match, will be skipped.')
-                    continue
-                p.copy_(torch.from_numpy(a))
+            P.take_over(arrays, full_assign, name_of=lambda k: f"dense::{k}")
             for k, bn in self._batch_norms().items():
                 if f"bn::{k}::mean" in arrays and arrays[f"bn::{k}::mean"].shape == tuple(bn.moving_mean.shape):
                     bn.moving_mean.copy_(torch.from_numpy(arrays[f"bn::{k}::mean"]))
                     bn.moving_var.copy_(torch.from_numpy(arrays[f"bn::{k}::var"]))
             if full_assign and "opt::step" in arrays:
-                if all_match and arrays["opt::dense_m"].shape == tuple(P.m.shape):
-                    P.m.copy_(torch.from_numpy(arrays["opt::dense_m"]))
-                    P.v.copy_(torch.from_numpy(arrays["opt::dense_v"]))
                 self.net.step = int(arrays["opt::step"])
 
     def _rebuild_sharded(self, path, model_name, full_assign):

@@ -74,6 +74,26 @@ class DenseParams:
     def zero_grad(self) -> None:
         self.grad.zero_()
 
+    @torch.no_grad()
+    def take_over(self, arrays, full_assign: bool, name_of=lambda k: k) -> bool:
+        """Retraining on merged data: every parameter whose saved array `arrays[name_of(name)]` has its shape is copied, each
+        other one is named in a notice and keeps its fresh values.  The flat Adam moments `opt::dense_m` / `opt::dense_v`
+        follow iff `full_assign`, every parameter matched and the saved buffers have this one's shape (a changed shape
+        shifts the offsets behind it).  Returns whether every parameter matched."""
+        all_match = True
+        for k, p in self.params.items():
+            a = arrays[name_of(k)] if name_of(k) in arrays else None
+            if a is None or tuple(a.shape) != tuple(p.shape):
+                all_match = False
+                print(f'variable "{k}" is not in the saved model or changed its shape, will be skipped.')
+                continue
+            p.copy_(torch.from_numpy(a))
+        if (full_assign and all_match and "opt::dense_m" in arrays and "opt::dense_v" in arrays
+                and tuple(arrays["opt::dense_m"].shape) == tuple(self.m.shape)):
+            self.m.copy_(torch.from_numpy(arrays["opt::dense_m"]))
+            self.v.copy_(torch.from_numpy(arrays["opt::dense_v"]))
+        return all_match
+
     def adam_step(self, hp) -> None:
         """`hp`: by-value hyper-parameters or an `ops.AdamCoefBuffer` (graph-captured steps)."""
         with torch.no_grad():

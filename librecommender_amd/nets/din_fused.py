@@ -22,6 +22,7 @@ unchanged every step.  Replays run on a dedicated non-default stream, ordered ag
 from __future__ import annotations
 
 import contextlib
+import gc
 import os
 import weakref
 from typing import Dict, Optional
@@ -96,8 +97,16 @@ class GraphRunner:
         side.wait_stream(torch.cuda.current_stream(self.device))
         torch.cuda.synchronize(self.device)
         g = torch.cuda.CUDAGraph(keep_graph=True)          # the hipGraph_t stays around: its nodes are checked before use
-        with torch.cuda.graph(g, stream=side):
-            st["out"] = build()
+        # no cyclic collection while the stream captures: a dead cycle of an earlier model (its graphs, pools and streams) would
+        # be finalised in the middle of the capture, and its release makes calls that a capturing process may not make
+        collects = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(g, stream=side):
+                st["out"] = build()
+        finally:
+            if collects:
+                gc.enable()
         torch.cuda.current_stream(self.device).wait_stream(side)
         try:
             self.check_kernel_nodes_only(g)

@@ -5,7 +5,8 @@ LSTM stack over the rows of `seq_embeds_var` that the behaviour window names; th
 The first recurrent layer reads `seq_embeds_var` in place through the window's ids (csrc/rnn.hip, no [B, L, D] gather) and
 its input gradient goes back to the table as one (id, gradient) stream, masked positions dropped with id -1.  The pointwise
 losses are `ops.mf_score` with the user-vector block as X; `bpr` and `norm_embed` are composed from torch ops on the gathered
-rows.  Variables and their TF1 Adam moments are `NamedTables`; recurrent, layer-norm and Dense parameters are `DenseParams`.
+rows.  Variables and their TF1 Adam moments are `NamedTables`; recurrent, layer-norm and Dense parameters are `DenseParams`;
+the tables, the pointwise losses and the tables' Adam step are `nets/seq_tower.py`'s.
 """
 from __future__ import annotations
 
@@ -14,15 +15,15 @@ import torch.nn.functional as F
 
 from .. import ops
 from ..layers import DenseParams
-from ..layers.embedding import glorot_uniform_
 from ..layers.recurrent import RnnStack
-from ..layers.row_adam import NamedTables, RowAdam
+from ..layers.row_adam import RowAdam
 from ..utils.device import to_device
+from .seq_tower import SeqTowerNet
 
 LOSSES = ("mse", "cross_entropy", "focal", "bpr")
 
 
-class RNN4RecNet(NamedTables):
+class RNN4RecNet(SeqTowerNet):
     def __init__(self, n_items, embed_size=16, hidden_units=(16,), rnn_type="gru", use_layer_norm=False, dropout_rate=0.0,
                  norm_embed=False, max_seq_len=10, lr=1e-3, epsilon=1e-5, seed=42, device=None, dense_adam=False,
                  loss="cross_entropy", reg=None):
@@ -39,20 +40,10 @@ class RNN4RecNet(NamedTables):
         self.P.add("dense/kernel", (self.rnn.n_out, self.K), "glorot_uniform")
         self.P.add("dense/bias", (self.K,), "zeros")
         self.P.finalize()
-        gen = torch.Generator(device=self.device)
-        gen.manual_seed(seed)
-        shapes = {"seq_embeds_var": (self.n_items + 1, int(hidden_units[0])), "item_embeds_var": (self.n_items, self.K)}
-        tables = {}
-        for name, shape in shapes.items():                                   # tf.glorot_uniform_initializer
-            tables[name] = torch.empty(shape, dtype=torch.float32, device=self.device)
-            glorot_uniform_(tables[name], shape, gen)
-        tables["item_bias_var"] = torch.zeros((self.n_items, 1), dtype=torch.float32, device=self.device)
-        super().__init__(tables)
+        self._init_tables({"seq_embeds_var": (self.n_items + 1, int(hidden_units[0])), "item_embeds_var": (self.n_items, self.K)},
+                          seed)
         self.gen = torch.Generator(device=self.device)
         self.gen.manual_seed(seed + 2)
-
-    def _i32(self, x):
-        return to_device(x, self.device).to(torch.int32).contiguous()
 
     # ---- user side ------------------------------------------------------------------------------
     def _user(self, ids, lens, masks=None):
@@ -65,33 +56,7 @@ class RNN4RecNet(NamedTables):
         u, _ = self._user(self._i32(seqs), self._i32(lens))
         return F.normalize(u, dim=1, eps=1e-12) if self.norm_embed else u
 
-    @torch.no_grad()
-    def item_matrix(self):
-        """[N, K] class rows (normalised if `norm_embed`) and [N] biases (dyn_embed_base.py:240-269)."""
-        w = self.vars["item_embeds_var"]
-        return (F.normalize(w, dim=1, eps=1e-12) if self.norm_embed else w), self.vars["item_bias_var"].view(-1)
-
     # ---- losses ---------------------------------------------------------------------------------
-    def _item_leaves(self, items):
-        q = ops.embed_gather(self.vars["item_embeds_var"], items.view(-1, 1)).view(-1, self.K).requires_grad_(True)
-        b = self.vars["item_bias_var"].view(-1)[items.long()].requires_grad_(True)
-        return q, b
-
-    def _pointwise_torch(self, u, items, labels):
-        """`rnn4rec.py:157-167` with `norm_embed`: both sides l2-normalised."""
-        q, b = self._item_leaves(items)
-        s = (F.normalize(u, dim=1, eps=1e-12) * F.normalize(q, dim=1, eps=1e-12)).sum(1) + b
-        if self.loss == "mse":
-            loss = F.mse_loss(s, labels)
-        else:
-            bce = F.binary_cross_entropy_with_logits(s, labels, reduction="none")
-            if self.loss == "focal":                                         # tfops/loss.py:56-62
-                p = torch.sigmoid(s)
-                bce = (labels * 0.25 + (1 - labels) * 0.75) * (1 - (labels * p + (1 - labels) * (1 - p))) ** 2.0 * bce
-            loss = bce.mean()
-        loss.backward()
-        return loss.detach(), q.grad, b.grad
-
     def _bpr_torch(self, u, pos, neg):
         """`rnn4rec.py:169-195`: -mean log sigmoid(b_p - b_n + <u, q_p - q_n>).  With `norm_embed` the reference normalises
         the item rows but takes the RAW user vector in the difference (rnn4rec.py:191 reads `self.user_embeds`)."""
@@ -109,7 +74,6 @@ class RNN4RecNet(NamedTables):
         """One step on a pointwise batch (`items`, `labels`) or, for `bpr`, on (`pos`, `neg`) pairs; `masks`: the dropout
         masks of `RnnStack.draw_masks` (drawn here when the net has a dropout rate)."""
         self.step += 1
-        V, M, S = self.vars, self.m, self.v
         ids, ln = self._i32(seqs), self._i32(lens)
         B, L = ids.shape
         if masks is None and self.rnn.dropout_rate > 0:
@@ -120,25 +84,11 @@ class RNN4RecNet(NamedTables):
             loss, it, gq, gb = self._bpr_torch(u, self._i32(pos), self._i32(neg))
         else:
             it = self._i32(items)
-            y = to_device(labels, self.device).to(torch.float32).contiguous()
-            if self.norm_embed:
-                loss, gq, gb = self._pointwise_torch(u, it, y)
-            else:
-                with torch.no_grad():
-                    slot = torch.arange(B, dtype=torch.int32, device=self.device)
-                    out = ops.mf_score(u.detach().contiguous(), V["item_embeds_var"], None, V["item_bias_var"].view(-1),
-                                       torch.zeros_like(slot), it, y, self.loss, xidx=slot, mode="grad", gscale=1.0 / B)
-                    loss, gq, gb = out["loss"].sum() / B, out["gq"], out["g"]
-                u.backward(out["gx"])
+            loss, gq, gb = self._pointwise(u, it, to_device(labels, self.device).to(torch.float32).contiguous())
         with torch.no_grad():
             hp = ops.adam_hp(self.lr, self.step, eps=self.epsilon, tf_style=True)
             t = torch.arange(L, dtype=torch.int32, device=self.device)
             sid = torch.where(t[None, :] < ln.clamp(0, L)[:, None], ids, torch.full_like(ids, -1)).reshape(-1).contiguous()
-            seg_s = self.adam.segments("seq", sid, self.n_items + 1)
-            self.adam.update(hp, seg_s, V["seq_embeds_var"], M["seq_embeds_var"], S["seq_embeds_var"],
-                             io.gx.reshape(B * L, -1))
-            seg_i = self.adam.segments("item", it.contiguous(), self.n_items)
-            self.adam.update(hp, seg_i, V["item_embeds_var"], M["item_embeds_var"], S["item_embeds_var"], gq.contiguous(),
-                             lin=(V["item_bias_var"], M["item_bias_var"], S["item_bias_var"], gb.contiguous()))
+            self._update_seq_and_items(hp, sid, io.gx.reshape(B * L, -1), it, gq, gb)
             self.P.adam_step(hp)
         return loss

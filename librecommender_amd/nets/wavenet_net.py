@@ -9,7 +9,8 @@ gradient buffer of `DenseParams` (the convolution parameters are its first tenso
 returns the input gradient as one (id, gradient) stream.  There is no sequence mask: pad positions carry the pad row
 (id == n_items), take part in every layer and in the pool, and the pad row is trained.  The pointwise losses are
 `ops.mf_score` with the [B, 2K] user block as X; `norm_embed` is composed from torch ops.  Variables and their TF1 Adam
-moments are `NamedTables`; convolution and Dense parameters are `DenseParams`.
+moments are `NamedTables`; convolution and Dense parameters are `DenseParams`; the tables, the pointwise losses and the
+tables' Adam step are `nets/seq_tower.py`'s.
 """
 from __future__ import annotations
 
@@ -18,9 +19,9 @@ import torch.nn.functional as F
 
 from .. import ops
 from ..layers import DenseParams
-from ..layers.embedding import glorot_uniform_
-from ..layers.row_adam import NamedTables, RowAdam
+from ..layers.row_adam import RowAdam
 from ..utils.device import to_device
+from .seq_tower import SeqTowerNet
 
 LOSSES = ("mse", "cross_entropy", "focal")
 
@@ -31,7 +32,9 @@ def conv_param_names(n_blocks, n_layers_per_block):
     return [(f"conv1d{'' if i == 0 else f'_{i}'}/kernel", f"conv1d{'' if i == 0 else f'_{i}'}/bias") for i in range(n)]
 
 
-class WaveNetNet(NamedTables):
+class WaveNetNet(SeqTowerNet):
+    bias_l2 = False          # the reference regularises item_embeds_var but not item_bias_var (wave_net.py:169-179)
+
     def __init__(self, n_users, n_items, embed_size=16, n_filters=16, n_blocks=1, n_layers_per_block=4, norm_embed=False,
                  max_seq_len=10, lr=1e-3, epsilon=1e-5, seed=42, device=None, dense_adam=False, loss="cross_entropy", reg=None):
         if loss not in LOSSES:
@@ -58,19 +61,8 @@ class WaveNetNet(NamedTables):
         n_conv = ops.wavenet_param_floats(self.K, self.F, self.n_blocks, self.n_per_block)
         self.conv_params, self.conv_grad = self.P.flat[:n_conv], self.P.grad[:n_conv]
         assert self.P["dense/kernel"].data_ptr() == self.P.flat.data_ptr() + 4 * n_conv, "DenseParams / lr_wavenet layout"
-        gen = torch.Generator(device=self.device)
-        gen.manual_seed(seed)
-        shapes = {"user_embeds_var": (self.n_users + 1, self.K), "seq_embeds_var": (self.n_items + 1, self.K),
-                  "item_embeds_var": (self.n_items, 2 * self.K)}
-        tables = {}
-        for name, shape in shapes.items():                                   # tf.glorot_uniform_initializer
-            tables[name] = torch.empty(shape, dtype=torch.float32, device=self.device)
-            glorot_uniform_(tables[name], shape, gen)
-        tables["item_bias_var"] = torch.zeros((self.n_items, 1), dtype=torch.float32, device=self.device)
-        super().__init__(tables)
-
-    def _i32(self, x):
-        return to_device(x, self.device).to(torch.int32).contiguous()
+        self._init_tables({"user_embeds_var": (self.n_users + 1, self.K), "seq_embeds_var": (self.n_items + 1, self.K),
+                           "item_embeds_var": (self.n_items, 2 * self.K)}, seed)
 
     # ---- user side ------------------------------------------------------------------------------
     def _stack(self, ids):
@@ -84,33 +76,10 @@ class WaveNetNet(NamedTables):
                        torch.addmm(self.P["dense/bias"], pooled, self.P["dense/kernel"])], dim=1)
         return F.normalize(u, dim=1, eps=1e-12) if self.norm_embed else u
 
-    @torch.no_grad()
-    def item_matrix(self):
-        """[N, 2K] class rows (normalised if `norm_embed`) and [N] biases (dyn_embed_base.py:240-269)."""
-        w = self.vars["item_embeds_var"]
-        return (F.normalize(w, dim=1, eps=1e-12) if self.norm_embed else w), self.vars["item_bias_var"].view(-1)
-
-    # ---- losses ---------------------------------------------------------------------------------
-    def _pointwise_torch(self, u, items, labels):
-        """`wave_net.py:145-152` with `norm_embed`: both sides l2-normalised."""
-        q = ops.embed_gather(self.vars["item_embeds_var"], items.view(-1, 1)).view(-1, 2 * self.K).requires_grad_(True)
-        b = self.vars["item_bias_var"].view(-1)[items.long()].requires_grad_(True)
-        s = (F.normalize(u, dim=1, eps=1e-12) * F.normalize(q, dim=1, eps=1e-12)).sum(1) + b
-        if self.loss == "mse":
-            loss = F.mse_loss(s, labels)
-        else:
-            bce = F.binary_cross_entropy_with_logits(s, labels, reduction="none")
-            if self.loss == "focal":                                         # tfops/loss.py:56-62
-                p = torch.sigmoid(s)
-                bce = (labels * 0.25 + (1 - labels) * 0.75) * (1 - (labels * p + (1 - labels) * (1 - p))) ** 2.0 * bce
-            loss = bce.mean()
-        loss.backward()
-        return loss.detach(), q.grad, b.grad
-
     # ---- one step ---------------------------------------------------------------------------------
     def train_step(self, users, seqs, items, labels):
         self.step += 1
-        V, M, S, K = self.vars, self.m, self.v, self.K
+        V, M, S = self.vars, self.m, self.v
         us, ids, it = self._i32(users), self._i32(seqs), self._i32(items)
         y = to_device(labels, self.device).to(torch.float32).contiguous()
         B, L = ids.shape
@@ -119,15 +88,7 @@ class WaveNetNet(NamedTables):
         urow = V["user_embeds_var"][us.long()].requires_grad_(True)
         pooled.requires_grad_(True)
         u = torch.cat([urow, torch.addmm(self.P["dense/bias"], pooled, self.P["dense/kernel"])], dim=1)
-        if self.norm_embed:
-            loss, gq, gb = self._pointwise_torch(u, it, y)
-        else:
-            with torch.no_grad():
-                slot = torch.arange(B, dtype=torch.int32, device=self.device)
-                out = ops.mf_score(u.detach().contiguous(), V["item_embeds_var"], None, V["item_bias_var"].view(-1),
-                                   torch.zeros_like(slot), it, y, self.loss, xidx=slot, mode="grad", gscale=1.0 / B)
-                loss, gq, gb = out["loss"].sum() / B, out["gq"], out["g"]
-            u.backward(out["gx"])
+        loss, gq, gb = self._pointwise(u, it, y)
         with torch.no_grad():
             gx, _ = ops.wavenet_bwd(V["seq_embeds_var"], ids, self.conv_params, self.F, self.n_blocks, self.n_per_block,
                                     acts, arg, pooled.grad.contiguous(), gparams=self.conv_grad)
@@ -136,16 +97,6 @@ class WaveNetNet(NamedTables):
             self.adam.update(hp, seg_u, V["user_embeds_var"], M["user_embeds_var"], S["user_embeds_var"], urow.grad.contiguous())
             inside = (ids >= 0) & (ids <= self.n_items)
             sid = torch.where(inside, ids, torch.full_like(ids, -1)).reshape(-1).contiguous()
-            seg_s = self.adam.segments("seq", sid, self.n_items + 1)
-            self.adam.update(hp, seg_s, V["seq_embeds_var"], M["seq_embeds_var"], S["seq_embeds_var"], gx.reshape(B * L, -1))
-            seg_i = self.adam.segments("item", it, self.n_items)
-            bias = (V["item_bias_var"], M["item_bias_var"], S["item_bias_var"], gb.contiguous())
-            if self.adam.dense and self.adam.l2:
-                # the reference regularises item_embeds_var but not item_bias_var (wave_net.py:169-179)
-                self.adam.update(hp, seg_i, V["item_embeds_var"], M["item_embeds_var"], S["item_embeds_var"], gq.contiguous())
-                ops.adam_dense(*bias[:3], hp, grows=ops.embed_segment_sum(bias[3].view(-1, 1), seg_i), seg=seg_i,
-                               row_slot=self.adam.row_slot(bias[0]), l2=0.0)
-            else:
-                self.adam.update(hp, seg_i, V["item_embeds_var"], M["item_embeds_var"], S["item_embeds_var"], gq.contiguous(), lin=bias)
+            self._update_seq_and_items(hp, sid, gx.reshape(B * L, -1), it, gq, gb)
             self.P.adam_step(hp)
         return loss
