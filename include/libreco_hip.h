@@ -1128,6 +1128,42 @@ int lr_wavenet_bwd_f32(const float* table, int64_t V, const int32_t* ids, int64_
                        int n_per_block, const float* params, const float* acts, const float* gpooled, const int32_t* arg,
                        float* gx, float* gparams, void* ws, size_t ws_bytes, lr_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * AutoInt — the interaction stack of libreco/algorithms/autoint.py:146-168 (layers/attention.py:67-101, the Keras
+ * MultiHeadAttention(use_bias=False) branch) and its Dense(1) read-out in one forward launch, f32 on the VALU.  T (fields), D
+ * (embedding width) and H * head_dims[l] in [1, 64], H in [1, 8], 1 to 8 layers (lr_autoint_supported, otherwise LR_ESHAPE).
+ * `head_dims` is a HOST array of n_layers ints, read during the call.  No float atomics anywhere: same bits from run to run.
+ *   A_0 = x [B, T, D] (read in place).  Layer l = 1 .. n_layers, hd = head_dims[l - 1], M = H * hd:
+ *     Q = A Wq, Kx = A Wk, V = A Wv (kernels [D, M], head h = columns [h hd, (h + 1) hd)); per head S = (Q_h / sqrt(hd)) Kx_h^T,
+ *     P = softmax(S) over the last axis with the row maximum subtracted, O_h = P V_h; Y = concat_h(O_h) Wo (Wo [M, D]);
+ *     A_l = A_{l-1} + Y if `residual`, else Y.  No mask, bias, activation or normalisation.
+ *   logits[b] = flatten(A_n[b]) . w + c (w [T * D], c [1]).
+ * Parameter layout (the contract; it is how layers/dense.py `DenseParams` lays out tensors added in this order): one f32
+ * buffer holding, per layer, the query, key, value and attention_output kernels (row-major [D, M], [D, M], [D, M], [M, D]),
+ * then dense/kernel [T * D] and dense/bias [1], every tensor starting on a 16-byte boundary (its length rounded up to 4
+ * floats; the gap is not read).  lr_autoint_params_bytes is the buffer's length.  `gparams` has the same layout; the backward
+ * writes every element of it (the gaps as 0).
+ *   forward   writes every element of logits [B] and, unless `acts` is NULL, of acts (lr_autoint_fwd_acts_bytes: [n_layers, B,
+ *             T, D] row-major, slab l - 1 = A_l).  acts == NULL is inference: nothing but the logits is written.  A sample's
+ *             logit has the same bits whatever batch it is part of and whether or not acts is written.  `saved`
+ *             (lr_autoint_fwd_saved_bytes, contents arbitrary on entry) is whatever else the backward wants: currently 0 bytes,
+ *             the backward recomputes Q, Kx, V, P and O from acts, and `saved` may be NULL.
+ *   backward  from glogits [B], with x, params and acts as the forward saw and left them: writes every element of gx [B, T, D]
+ *             and gparams.  Parameter gradients are summed over the batch as per-workgroup partials in `ws`
+ *             (lr_autoint_bwd_ws_bytes bytes, contents arbitrary on entry) added in workgroup order.
+ * ---------------------------------------------------------------------------------- */
+int lr_autoint_supported(int T, int D, int H, int n_layers, const int* head_dims);
+size_t lr_autoint_params_bytes(int T, int D, int H, int n_layers, const int* head_dims);
+size_t lr_autoint_fwd_acts_bytes(int64_t B, int T, int D, int n_layers);
+size_t lr_autoint_fwd_saved_bytes(int64_t B, int T, int D, int H, int n_layers, const int* head_dims);
+size_t lr_autoint_bwd_ws_bytes(int64_t B, int T, int D, int H, int n_layers, const int* head_dims);
+int lr_autoint_fwd_f32(const float* x, int64_t B, int T, int D, int H, int n_layers, const int* head_dims, int residual,
+                       const float* params, float* acts, size_t acts_bytes, void* saved, size_t saved_bytes, float* logits,
+                       lr_stream_t stream);
+int lr_autoint_bwd_f32(const float* x, int64_t B, int T, int D, int H, int n_layers, const int* head_dims, int residual,
+                       const float* params, const float* acts, const void* saved, const float* glogits, float* gx,
+                       float* gparams, void* ws, size_t ws_bytes, lr_stream_t stream);
+
 /* Measurement probe (scripts/mfma_peak.py): iters x 8 back-to-back v_mfma_f32_32x32x2_f32 per wave on
  * 256 x waves_per_simd workgroups — the f32 MFMA rate the chip sustains at the clock it holds under that load. */
 int lr_mfma_f32_probe(int iters, int waves_per_simd, float* out, lr_stream_t stream);

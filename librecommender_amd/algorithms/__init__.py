@@ -1,4 +1,5 @@
 from .als import ALS
+from .autoint import AutoInt
 from .bpr import BPR
 from .din import DIN
 from .fm import FM, DeepFM
@@ -17,4 +18,4 @@ from .wavenet import WaveNet
 from .youtube_ranking import YouTubeRanking
 from .youtube_retrieval import YouTubeRetrieval
 
-__all__ = ["ALS", "BPR", "DIN", "DeepFM", "FM", "ItemCF", "LightGCN", "NGCF", "RNN4Rec", "SIM", "SVD", "SVDpp", "Swing", "Transformer", "TwoTower", "UserCF", "WaveNet", "YouTubeRanking", "YouTubeRetrieval"]
+__all__ = ["ALS", "AutoInt", "BPR", "DIN", "DeepFM", "FM", "ItemCF", "LightGCN", "NGCF", "RNN4Rec", "SIM", "SVD", "SVDpp", "Swing", "Transformer", "TwoTower", "UserCF", "WaveNet", "YouTubeRanking", "YouTubeRetrieval"]

@@ -2227,3 +2227,84 @@ def wavenet_bwd(table: torch.Tensor, ids: torch.Tensor, params: torch.Tensor, F:
     _call("lr_wavenet_bwd_f32", _ptr(table), V, _ptr(ids), B, L, D, F, n_blocks, n_per_block, _ptr(params), _ptr(acts),
           _ptr(gpooled), _ptr(arg), _ptr(gx), _ptr(gparams), _ptr(ws), ws.numel(), _stream())
     return gx, gparams
+
+
+# --------------------------------------------------------------------------------------
+# AutoInt stack (csrc/autoint.hip)
+# --------------------------------------------------------------------------------------
+def _head_dims(head_dims):
+    """The per-layer head dimensions as the host int array the entry points read."""
+    dims = [int(h) for h in head_dims]
+    return len(dims), (_lib.C.c_int * max(len(dims), 1))(*dims)
+
+
+def autoint_supported(T: int, D: int, H: int, head_dims) -> bool:
+    """Whether the AutoInt kernels take `T` fields of width `D`, `H` heads and these per-layer head dimensions."""
+    n, hd = _head_dims(head_dims)
+    return bool(_lib.load().lr_autoint_supported(int(T), int(D), int(H), n, hd))
+
+
+def autoint_param_floats(T: int, D: int, H: int, head_dims) -> int:
+    """Length of the parameter buffer (per layer the query, key, value [D, H hd] and attention_output [H hd, D] kernels, then
+    dense/kernel [T D] and dense/bias [1], every tensor on a 16-byte boundary: the layout `DenseParams` gives tensors added in
+    that order); 0 for an unsupported shape."""
+    n, hd = _head_dims(head_dims)
+    return _lib.load().lr_autoint_params_bytes(int(T), int(D), int(H), n, hd) // 4
+
+
+def _autoint_check(x, params, H, head_dims):
+    """-> (B, T, D, n_layers, host head dimensions) of one AutoInt call, its operands validated."""
+    B, T, D = _req(x, torch.float32, "x", 3).shape
+    _req(params, torch.float32, "params", 1)
+    if not autoint_supported(T, D, H, head_dims):
+        raise ValueError(f"unsupported AutoInt shape: T={T}, D={D}, H={H}, head_dims={tuple(head_dims)} (T, D and H * head_dim "
+                         "from 1 to 64, 1 to 8 heads, 1 to 8 layers)")
+    if params.numel() != autoint_param_floats(T, D, H, head_dims):
+        raise ValueError("params must be the flat parameter buffer of this shape (see `autoint_param_floats`)")
+    if params.data_ptr() % 16:
+        raise ValueError("params must start on a 16-byte boundary")
+    n, hd = _head_dims(head_dims)
+    return B, T, D, n, hd
+
+
+def autoint_fwd(x: torch.Tensor, params: torch.Tensor, H: int, head_dims, residual: bool = True, want_acts: bool = True):
+    """`lr_autoint_fwd_f32`: the attention stack over x [B, T, D] and the Dense(1) read-out.  Returns (logits [B], acts
+    [n_layers, B, T, D] — slab l - 1 is the output of layer l —, saved: the opaque bytes `autoint_bwd` wants next to acts);
+    without `want_acts` acts and saved are None: inference, only the logits are written."""
+    B, T, D, n, hd = _autoint_check(x, params, H, head_dims)
+    dev = x.device
+    logits = torch.empty(max(B, 1), dtype=torch.float32, device=dev)[:B]
+    acts = torch.empty((n, max(B, 1), T, D), dtype=torch.float32, device=dev)[:, :B] if want_acts else None
+    saved = torch.empty(_lib.load().lr_autoint_fwd_saved_bytes(B, T, D, int(H), n, hd), dtype=torch.uint8,
+                        device=dev) if want_acts else None
+    if B == 0:
+        return logits, acts, saved
+    _call("lr_autoint_fwd_f32", _ptr(x), B, T, D, int(H), n, hd, int(bool(residual)), _ptr(params), _ptr(acts),
+          0 if acts is None else acts.numel() * 4, _ptr(saved), 0 if saved is None else saved.numel(), _ptr(logits), _stream())
+    return logits, acts, saved
+
+
+def autoint_bwd(x: torch.Tensor, params: torch.Tensor, H: int, head_dims, residual: bool, acts: torch.Tensor,
+                saved: torch.Tensor, glogits: torch.Tensor, gparams: Optional[torch.Tensor] = None):
+    """`lr_autoint_bwd_f32`: from glogits [B] -> (gx [B, T, D], gparams in the layout of `params`); `gparams` may be given (e.g.
+    a slice of `DenseParams.grad`) and is overwritten.  Parameter gradients are summed in a fixed order."""
+    B, T, D, n, hd = _autoint_check(x, params, H, head_dims)
+    dev = x.device
+    if _req(acts, torch.float32, "acts", 4).shape != (n, B, T, D):
+        raise ValueError("acts must be the forward's [n_layers, B, T, D]")
+    if _req(glogits, torch.float32, "glogits", 1).shape != (B,):
+        raise ValueError("glogits must be [B]")
+    if _req(saved, torch.uint8, "saved", 1).numel() != _lib.load().lr_autoint_fwd_saved_bytes(B, T, D, int(H), n, hd):
+        raise ValueError("saved must be the forward's (see `autoint_fwd`)")
+    if gparams is None:
+        gparams = torch.empty_like(params)
+    elif _req(gparams, torch.float32, "gparams", 1).numel() != params.numel():
+        raise ValueError("gparams must have the length of params")
+    gx = torch.empty((max(B, 1), T, D), dtype=torch.float32, device=dev)[:B]
+    if B == 0:
+        gparams.zero_()
+        return gx, gparams
+    ws = torch.empty(max(_lib.load().lr_autoint_bwd_ws_bytes(B, T, D, int(H), n, hd), 256), dtype=torch.uint8, device=dev)
+    _call("lr_autoint_bwd_f32", _ptr(x), B, T, D, int(H), n, hd, int(bool(residual)), _ptr(params), _ptr(acts),
+          _ptr(saved), _ptr(glogits), _ptr(gx), _ptr(gparams), _ptr(ws), ws.numel(), _stream())
+    return gx, gparams
