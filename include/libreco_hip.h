@@ -1164,6 +1164,63 @@ int lr_autoint_bwd_f32(const float* x, int64_t B, int T, int D, int H, int n_lay
                        const float* params, const float* acts, const void* saved, const float* glogits, float* gx,
                        float* gparams, void* ws, size_t ws_bytes, lr_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Skip-gram word2vec in windows: the training of Item2Vec and DeepWalk, which the reference leaves to
+ * gensim.Word2Vec on CPU threads (libreco/bases/gensim_base.py, algorithms/item2vec.py, algorithms/deepwalk.py).  The word
+ * index is the item's inner id.  Every random choice is H(seed, stream, a, b) = mix64(mix64(mix64(seed + G stream) + G (a + 1))
+ * + G (b + 1)), G = 0x9e3779b97f4a7c15, mix64 the splitmix64 finaliser: integers are bit-exact against tests/w2v_oracle.py.
+ * Rows are D = 1 .. 256 floats (lr_w2v_supported, otherwise LR_ESHAPE).  An id outside its table takes no part.  No float
+ * atomics: same bits from run to run.
+ *   walks        walk w starts at starts[w] and takes up to walk_length - 1 steps over the successor CSR (succ_ptr [n_items + 1],
+ *                succ_idx [n_edges], duplicates kept): successor number (hi32(H(seed, 1, pass, w walk_length + step)) * degree)
+ *                >> 32.  A node without successors ends the walk.  Writes walks [n_walks, walk_length] (-1 padded) and lens.
+ *   keep         keep[i] = hi32(H(seed, 2, epoch, i)) < keep_thr[tokens[i]] (keep_thr [n_items]: the host's
+ *                floor(2^32 * keep probability), 0 for a word that never occurs).
+ *   pairs        over the compacted corpus (ctok the kept tokens, craw their raw positions, csent their sentence, cptr
+ *                [n_sent + 1] the compacted sentence starts): position i has reach r = window - H(seed, 3, epoch, craw[i]) % window
+ *                and emits (input ctok[j], predicted ctok[i], centre craw[i]) for every j != i in [i - r, i + r] inside
+ *                the sentence, in ascending (i, j).  `count` writes the number per position; `emit` takes their exclusive
+ *                scan `offs` and writes at most n_pairs pairs.
+ *   targets      per pair p, LR_W2V_NEGATIVES + 1 slots and then the Huffman path of the predicted word (hs_ptr [n_items + 1],
+ *                hs_nodes / hs_codes [hs_len]; hs_ptr NULL: none).  offs == NULL counts (lens[p]); otherwise offs [W + 1] is
+ *                the exclusive scan of lens and rows / labels / slot_in [n_slots] are filled: the predicted word (label 1),
+ *                the draws k = 0 .. 4: the first word whose cum[] exceeds hi32(H(seed, 4, epoch, (pair_base + p) * 5 + k))
+ *                (cum [n_items]: the host's cumulative count^0.75 table scaled to 2^32; label 0; row -1 when the draw is the
+ *                predicted word), then (node row, 1 - code) along the path.  slot_in repeats the pair's input id per slot.
+ *   score        one row group per pair of a window: f = syn0[in] . syn1[row] per target, g = (label - 1 / (1 + expf(-f))) *
+ *                alpha, 0 when |f| >= 6, the row is outside [0, V1) or the input id is outside [0, n_items); alpha =
+ *                max(1e-4, 0.025 - (0.025 - 1e-4) * (pos0 + centre[p]) * inv_total).  Writes g at every slot of the window's
+ *                pairs, stash [W, D] (row p = sum of g * syn1[row]) and, unless NULL, loss [W] (the sum of -log sigmoid(+-f)
+ *                over the pair's live targets).  offs holds W + 1 entries that index rows / labels / g (n_slots long).
+ *   out_update   the ordered update of the touched rows of `table` (runs of lr_segments_build over n positions).  With
+ *                slot_in: position q adds g[q] * other[slot_in[q]] (the output table; other = syn0, other_rows = n_items; g
+ *                and slot_in point at the window's first slot).  With g and slot_in NULL: position q adds other[q] (the
+ *                input table; other = the stash, other_rows >= n).  Ascending position within a row.
+ * ---------------------------------------------------------------------------------- */
+#define LR_W2V_NEGATIVES 5
+int lr_w2v_supported(int D);
+int lr_w2v_walks_i32(const int32_t* starts, int64_t n_walks, int walk_length, const int64_t* succ_ptr,
+                     const int32_t* succ_idx, int64_t n_items, int64_t n_edges, uint64_t seed, int64_t pass,
+                     int32_t* walks, int32_t* lens, lr_stream_t stream);
+int lr_w2v_keep_u8(const int32_t* tokens, int64_t n, const int64_t* keep_thr, int64_t n_items, uint64_t seed,
+                   int64_t epoch, uint8_t* keep, lr_stream_t stream);
+int lr_w2v_pairs_count_i32(const int32_t* craw, const int32_t* csent, const int64_t* cptr, int64_t nc, int64_t n_sent,
+                           int window, uint64_t seed, int64_t epoch, int32_t* counts, lr_stream_t stream);
+int lr_w2v_pairs_emit_i32(const int32_t* ctok, const int32_t* craw, const int32_t* csent, const int64_t* cptr, int64_t nc,
+                          int64_t n_sent, int window, uint64_t seed, int64_t epoch, const int64_t* offs, int64_t n_pairs,
+                          int32_t* in_ids, int32_t* pred, int32_t* centre, lr_stream_t stream);
+int lr_w2v_targets_i32(const int32_t* in_ids, const int32_t* pred, int64_t W, int64_t pair_base, int64_t n_items,
+                       const int64_t* cum, const int32_t* hs_ptr, const int32_t* hs_nodes, const int32_t* hs_codes,
+                       int64_t hs_len, uint64_t seed, int64_t epoch, const int64_t* offs, int32_t* lens, int64_t n_slots,
+                       int32_t* rows, int32_t* labels, int32_t* slot_in, lr_stream_t stream);
+int lr_w2v_score_f32(const float* syn0, int64_t n_items, const float* syn1, int64_t V1, int D, const int32_t* in_ids,
+                     const int32_t* centre, int64_t W, const int64_t* offs, const int32_t* rows, const int32_t* labels,
+                     int64_t n_slots, double pos0, double inv_total, float* g, float* stash, float* loss,
+                     lr_stream_t stream);
+int lr_w2v_out_update_f32(float* table, int64_t V, int D, const int32_t* seg_pos, const int32_t* seg_rows,
+                          const int32_t* seg_start, const int32_t* n_seg, int64_t n, const float* g, const int32_t* slot_in,
+                          const float* other, int64_t other_rows, lr_stream_t stream);
+
 /* Measurement probe (scripts/mfma_peak.py): iters x 8 back-to-back v_mfma_f32_32x32x2_f32 per wave on
  * 256 x waves_per_simd workgroups — the f32 MFMA rate the chip sustains at the clock it holds under that load. */
 int lr_mfma_f32_probe(int iters, int waves_per_simd, float* out, lr_stream_t stream);

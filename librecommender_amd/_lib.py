@@ -248,6 +248,16 @@ SIGNATURES = {
     "lr_autoint_bwd_ws_bytes": (_sz, [_i64, _int, _int, _int, _int, _p]),
     "lr_autoint_fwd_f32": (_int, [_p, _i64, _int, _int, _int, _int, _p, _int, _p, _p, _sz, _p, _sz, _p, _p]),
     "lr_autoint_bwd_f32": (_int, [_p, _i64, _int, _int, _int, _int, _p, _int, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "lr_w2v_supported": (_int, [_int]),
+    "lr_w2v_walks_i32": (_int, [_p, _i64, _int, _p, _p, _i64, _i64, C.c_uint64, _i64, _p, _p, _p]),
+    "lr_w2v_keep_u8": (_int, [_p, _i64, _p, _i64, C.c_uint64, _i64, _p, _p]),
+    "lr_w2v_pairs_count_i32": (_int, [_p, _p, _p, _i64, _i64, _int, C.c_uint64, _i64, _p, _p]),
+    "lr_w2v_pairs_emit_i32": (_int, [_p, _p, _p, _p, _i64, _i64, _int, C.c_uint64, _i64, _p, _i64, _p, _p, _p, _p]),
+    "lr_w2v_targets_i32": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _i64, C.c_uint64, _i64, _p, _p, _i64, _p, _p, _p,
+                                  _p]),
+    "lr_w2v_score_f32": (_int, [_p, _i64, _p, _i64, _int, _p, _p, _i64, _p, _p, _p, _i64, C.c_double, C.c_double, _p, _p, _p,
+                                _p]),
+    "lr_w2v_out_update_f32": (_int, [_p, _i64, _int, _p, _p, _p, _p, _i64, _p, _p, _p, _i64, _p]),
 }
 
 _lib = None

@@ -1,8 +1,10 @@
 from .als import ALS
 from .autoint import AutoInt
 from .bpr import BPR
+from .deepwalk import DeepWalk
 from .din import DIN
 from .fm import FM, DeepFM
+from .item2vec import Item2Vec
 from .item_cf import ItemCF
 from .lightgcn import LightGCN
 from .ngcf import NGCF
@@ -18,4 +20,4 @@ from .wavenet import WaveNet
 from .youtube_ranking import YouTubeRanking
 from .youtube_retrieval import YouTubeRetrieval
 
-__all__ = ["ALS", "AutoInt", "BPR", "DIN", "DeepFM", "FM", "ItemCF", "LightGCN", "NGCF", "RNN4Rec", "SIM", "SVD", "SVDpp", "Swing", "Transformer", "TwoTower", "UserCF", "WaveNet", "YouTubeRanking", "YouTubeRetrieval"]
+__all__ = ["ALS", "AutoInt", "BPR", "DIN", "DeepFM", "DeepWalk", "FM", "Item2Vec", "ItemCF", "LightGCN", "NGCF", "RNN4Rec", "SIM", "SVD", "SVDpp", "Swing", "Transformer", "TwoTower", "UserCF", "WaveNet", "YouTubeRanking", "YouTubeRetrieval"]

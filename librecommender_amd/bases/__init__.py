@@ -3,5 +3,8 @@ from .cf_base import CfBase
 from .embed_base import EmbedBase
 from .dyn_embed_base import DynEmbedBase
 from .feat_base import FeatBase
+from .word2vec_base import Word2VecBase
 
-__all__ = ["Base", "CfBase", "EmbedBase", "DynEmbedBase", "FeatBase"]
+GensimBase = Word2VecBase      # the reference's name for this base
+
+__all__ = ["Base", "CfBase", "EmbedBase", "DynEmbedBase", "FeatBase", "Word2VecBase", "GensimBase"]

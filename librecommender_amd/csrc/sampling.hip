@@ -8,14 +8,9 @@
 // cannot be reproduced on a device, so this is an opt-in sampler with its own (bit-exact) oracle
 // (oracle/ops_np.py:sample_negatives_counter); the host collators stay the reference-exact path.
 #include "common.hpp"
+#include "mix64.hpp"
 
 namespace lr {
-
-__host__ __device__ inline uint64_t mix64(uint64_t z) {   // splitmix64 finaliser
-  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-  return z ^ (z >> 31);
-}
 
 __device__ __forceinline__ bool in_sorted(const int32_t* __restrict__ a, int64_t lo, int64_t hi,
                                           int32_t x) {

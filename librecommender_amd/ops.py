@@ -2308,3 +2308,161 @@ def autoint_bwd(x: torch.Tensor, params: torch.Tensor, H: int, head_dims, residu
     _call("lr_autoint_bwd_f32", _ptr(x), B, T, D, int(H), n, hd, int(bool(residual)), _ptr(params), _ptr(acts),
           _ptr(saved), _ptr(glogits), _ptr(gx), _ptr(gparams), _ptr(ws), ws.numel(), _stream())
     return gx, gparams
+
+
+# --------------------------------------------------------------------------------------
+# skip-gram word2vec in windows (csrc/word2vec.hip)
+# --------------------------------------------------------------------------------------
+W2V_NEGATIVES = 5
+_U64 = (1 << 64) - 1
+
+
+def w2v_supported(embed_size: int) -> bool:
+    """Whether the word2vec kernels take rows of `embed_size` floats (1 to 256)."""
+    return bool(_lib.load().lr_w2v_supported(int(embed_size)))
+
+
+def w2v_walks(starts: torch.Tensor, succ_ptr: torch.Tensor, succ_idx: torch.Tensor, n_items: int, walk_length: int, seed: int,
+              pass_no: int):
+    """`lr_w2v_walks_i32`: one random walk per entry of `starts` over the successor CSR -> (walks [n, walk_length] int32 padded
+    with -1, lens [n] int32)."""
+    _req(starts, torch.int32, "starts", 1)
+    _req(succ_ptr, torch.int64, "succ_ptr", 1)
+    _req(succ_idx, torch.int32, "succ_idx", 1)
+    if succ_ptr.numel() != int(n_items) + 1:
+        raise ValueError("succ_ptr must hold n_items + 1 entries")
+    if walk_length < 1:
+        raise ValueError("`walk_length` must be at least 1")
+    n, L = starts.numel(), int(walk_length)
+    walks = torch.empty((max(n, 1), L), dtype=torch.int32, device=starts.device)[:n]
+    lens = torch.empty(max(n, 1), dtype=torch.int32, device=starts.device)[:n]
+    _call("lr_w2v_walks_i32", _ptr(starts), n, L, _ptr(succ_ptr), _ptr(succ_idx), int(n_items), succ_idx.numel(),
+          int(seed) & _U64, int(pass_no), _ptr(walks), _ptr(lens), _stream())
+    return walks, lens
+
+
+def w2v_keep(tokens: torch.Tensor, keep_thr: torch.Tensor, seed: int, epoch: int) -> torch.Tensor:
+    """`lr_w2v_keep_u8`: the subsampling flag of every raw token (`keep_thr` [n_items] int64: 2^32 * keep probability)."""
+    _req(tokens, torch.int32, "tokens", 1)
+    _req(keep_thr, torch.int64, "keep_thr", 1)
+    n = tokens.numel()
+    keep = torch.empty(max(n, 1), dtype=torch.uint8, device=tokens.device)[:n]
+    _call("lr_w2v_keep_u8", _ptr(tokens), n, _ptr(keep_thr), keep_thr.numel(), int(seed) & _U64, int(epoch), _ptr(keep),
+          _stream())
+    return keep
+
+
+def w2v_pairs(ctok: torch.Tensor, craw: torch.Tensor, csent: torch.Tensor, cptr: torch.Tensor, window: int, seed: int,
+              epoch: int):
+    """`lr_w2v_pairs_count_i32` / `lr_w2v_pairs_emit_i32` over the compacted corpus -> (in_ids, pred, centre), int32 [n_pairs]
+    in ascending (centre, context) order.  The scan between the two passes is a torch op; the pair count is read back once."""
+    for t_, n_ in ((ctok, "ctok"), (craw, "craw"), (csent, "csent")):
+        _req(t_, torch.int32, n_, 1)
+    _req(cptr, torch.int64, "cptr", 1)
+    nc, n_sent = ctok.numel(), cptr.numel() - 1
+    if craw.numel() != nc or csent.numel() != nc or n_sent < 0:
+        raise ValueError("shape mismatch")
+    if window < 1:
+        raise ValueError("`window_size` must be at least 1")
+    dev = ctok.device
+    counts = torch.empty(max(nc, 1), dtype=torch.int32, device=dev)[:nc]
+    args = (_ptr(craw), _ptr(csent), _ptr(cptr), nc, n_sent, int(window), int(seed) & _U64, int(epoch))
+    _call("lr_w2v_pairs_count_i32", *args, _ptr(counts), _stream())
+    incl = torch.cumsum(counts, 0, dtype=torch.int64)
+    n_pairs = int(incl[-1].item()) if nc else 0
+    if n_pairs >= 1 << 31:
+        raise ValueError("an epoch of 2^31 pairs or more is not supported")
+    offs = (incl - counts).contiguous()
+    out = [torch.empty(max(n_pairs, 1), dtype=torch.int32, device=dev)[:n_pairs] for _ in range(3)]
+    _call("lr_w2v_pairs_emit_i32", _ptr(ctok), *args, _ptr(offs), n_pairs, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream())
+    return tuple(out)
+
+
+def w2v_targets(in_ids: torch.Tensor, pred: torch.Tensor, cum: torch.Tensor, seed: int, epoch: int, pair_base: int = 0,
+                hs=None) -> dict:
+    """`lr_w2v_targets_i32` (count, a torch scan, fill) for the given pairs -> {"offs" int64 [W + 1], "rows", "labels",
+    "slot_in" int32 [n_slots]}.  `hs` is None (negatives only: the offsets are 6 p, nothing is read back) or the Huffman CSR
+    (hs_ptr [n_items + 1], hs_nodes, hs_codes), int32; then the slot count is read back."""
+    _req(in_ids, torch.int32, "in_ids", 1)
+    _req(pred, torch.int32, "pred", 1)
+    _req(cum, torch.int64, "cum", 1)
+    W, n_items, dev = pred.numel(), cum.numel(), pred.device
+    if in_ids.numel() != W:
+        raise ValueError("shape mismatch")
+    hp = hn = hc = None
+    if hs is not None:
+        hp, hn, hc = (_req(t_, torch.int32, n_, 1) for t_, n_ in zip(hs, ("hs_ptr", "hs_nodes", "hs_codes")))
+        if hp.numel() != n_items + 1 or hn.numel() != hc.numel():
+            raise ValueError("the Huffman CSR must hold n_items + 1 offsets and one code per node")
+    head = (_ptr(in_ids), _ptr(pred), W, int(pair_base), n_items, _ptr(cum), _ptr(hp), _ptr(hn), _ptr(hc),
+            0 if hn is None else hn.numel(), int(seed) & _U64, int(epoch))
+    offs = torch.zeros(W + 1, dtype=torch.int64, device=dev)
+    if hs is None:
+        torch.arange(0, (W + 1) * (W2V_NEGATIVES + 1), W2V_NEGATIVES + 1, out=offs)
+        n_slots = W * (W2V_NEGATIVES + 1)
+    else:
+        lens = torch.empty(max(W, 1), dtype=torch.int32, device=dev)[:W]
+        _call("lr_w2v_targets_i32", *head, None, _ptr(lens), 0, None, None, None, _stream())
+        torch.cumsum(lens, 0, dtype=torch.int64, out=offs[1:])
+        n_slots = int(offs[-1].item())
+    if n_slots >= 1 << 31:
+        raise ValueError("2^31 target slots or more in one call are not supported")
+    rows, labels, slot_in = (torch.empty(max(n_slots, 1), dtype=torch.int32, device=dev)[:n_slots] for _ in range(3))
+    _call("lr_w2v_targets_i32", *head, _ptr(offs), None, n_slots, _ptr(rows), _ptr(labels), _ptr(slot_in), _stream())
+    return {"offs": offs, "rows": rows, "labels": labels, "slot_in": slot_in}
+
+
+def w2v_score(syn0: torch.Tensor, syn1: torch.Tensor, in_ids: torch.Tensor, centre: torch.Tensor, offs: torch.Tensor,
+              rows: torch.Tensor, labels: torch.Tensor, pos0: float, inv_total: float, g: Optional[torch.Tensor] = None,
+              stash: Optional[torch.Tensor] = None, want_loss: bool = True):
+    """`lr_w2v_score_f32` over the W pairs of a window (`offs` [W + 1] indexes `rows` / `labels` / `g`, which may cover more
+    than the window) -> (g [n_slots], stash [W, D], loss [W] or None).  `g` and `stash` may be preallocated."""
+    _req(syn0, torch.float32, "syn0", 2)
+    _req(syn1, torch.float32, "syn1", 2)
+    _req(in_ids, torch.int32, "in_ids", 1)
+    _req(centre, torch.int32, "centre", 1)
+    _req(offs, torch.int64, "offs", 1)
+    _req(rows, torch.int32, "rows", 1)
+    _req(labels, torch.int32, "labels", 1)
+    D, W, n_slots, dev = syn0.shape[1], in_ids.numel(), rows.numel(), syn0.device
+    if not w2v_supported(D):
+        raise ValueError(f"the word2vec kernels take rows of 1 to 256 floats, got {D}")
+    if syn1.shape[1] != D or centre.numel() != W or offs.numel() != W + 1 or labels.numel() != n_slots:
+        raise ValueError("shape mismatch")
+    if g is None:
+        g = torch.empty(max(n_slots, 1), dtype=torch.float32, device=dev)[:n_slots]
+    elif _req(g, torch.float32, "g", 1).numel() < n_slots:
+        raise ValueError("g is too small")
+    if stash is None:
+        stash = torch.empty((max(W, 1), D), dtype=torch.float32, device=dev)[:W]
+    elif _req(stash, torch.float32, "stash", 2).shape[1] != D or stash.shape[0] < W:
+        raise ValueError("stash is too small")
+    loss = torch.empty(max(W, 1), dtype=torch.float32, device=dev)[:W] if want_loss else None
+    _call("lr_w2v_score_f32", _ptr(syn0), syn0.shape[0], _ptr(syn1), syn1.shape[0], D, _ptr(in_ids), _ptr(centre), W, _ptr(offs),
+          _ptr(rows), _ptr(labels), n_slots, float(pos0), float(inv_total), _ptr(g), _ptr(stash), _ptr(loss), _stream())
+    return g, stash, loss
+
+
+def w2v_out_update(table: torch.Tensor, seg: Segments, other: torch.Tensor, g: Optional[torch.Tensor] = None,
+                   slot_in: Optional[torch.Tensor] = None) -> None:
+    """`lr_w2v_out_update_f32`: the ordered update of one window's touched rows of `table` [V, D].  Output rows: `seg` over
+    the window's flat target rows, `g` / `slot_in` the window's slices and `other` = syn0.  Input rows: `seg` over the window's
+    input ids, `g` / `slot_in` None and `other` = the stash (at least `seg.n` rows)."""
+    _req(table, torch.float32, "table", 2)
+    _req(other, torch.float32, "other", 2)
+    V, D = table.shape
+    if not w2v_supported(D):
+        raise ValueError(f"the word2vec kernels take rows of 1 to 256 floats, got {D}")
+    if (g is None) != (slot_in is None):
+        raise ValueError("`g` and `slot_in` go together")
+    if g is not None:
+        _req(g, torch.float32, "g", 1)
+        _req(slot_in, torch.int32, "slot_in", 1)
+        if g.numel() < seg.n or slot_in.numel() < seg.n:
+            raise ValueError("g and slot_in must cover the segmented positions")
+    elif other.shape[0] < seg.n:
+        raise ValueError("the stash must hold one row per segmented position")
+    if V != seg.V or other.shape[1] != D:
+        raise ValueError("shape mismatch")
+    _call("lr_w2v_out_update_f32", _ptr(table), V, D, _ptr(seg.pos), _ptr(seg.rows), _ptr(seg.start), _ptr(seg.n_seg), seg.n,
+          _ptr(g), _ptr(slot_in), _ptr(other), other.shape[0], _stream())
