@@ -1129,6 +1129,40 @@ int lr_wavenet_bwd_f32(const float* table, int64_t V, const int32_t* ids, int64_
                        float* gx, float* gparams, void* ws, size_t ws_bytes, lr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Caser — the user side of libreco/algorithms/caser.py:177-221 up to the Dense layer, in one forward launch, f32 on the VALU.
+ * L (window) in [1, 64], K (table width) in [1, 128], nh and nv (horizontal and vertical filters) in [1, 64]
+ * (lr_caser_supported, otherwise LR_ESHAPE).  No float atomics anywhere: same bits from run to run.
+ *   x[b, t] = table[ids[b, t]] (table [V, K], ids int32 [B, L], read in place; an id outside [0, V) is never dereferenced: a
+ *   zero input row, gx exactly 0).  There is no sequence mask: pad positions take part like any other.
+ *   horizontal, i = 1 .. L:  z_i[b, t, f] = relu(bh_i[f] + sum_{tau < i, c < K} x[b, t + tau, c] Wh_i[tau, c, f]), t = 0 .. L - i
+ *                            (one fmaf chain from the bias, tau ascending, c ascending: positions with equal receptive fields
+ *                            give equal bits); h_i[b, f] = max_t z_i, arg = the smallest t that attains it
+ *   vertical:                v[b, c, g] = relu(bv[g] + sum_t x[b, t, c] Wv[t, g]) (one chain, t ascending)
+ *   feat[b] = concat(h_1, .., h_L, v flattened [c][g]), width L nh + K nv; arg int32 [B, L nh] in the order of feat.  A sample's
+ *   row has the same bits whatever batch it is part of and whether or not arg is written.  ReLU's derivative at 0 is 0: a
+ *   filter whose every position is <= 0 has feat == 0, arg == 0 and passes no gradient.
+ * Parameter layout (the contract; it is how layers/dense.py `DenseParams` lays out tensors added in this order): one f32
+ * buffer holding, for i = 1 .. L, Wh_i (row-major [i, K, nh]) then bh_i [nh], then Wv (row-major [1, L, nv]) and bv [nv],
+ * every tensor starting on a 16-byte boundary (its length rounded up to 4 floats; the gap is not read).
+ * lr_caser_params_bytes is the buffer's length.  `gparams` has the same layout; the backward writes every element of it (the
+ * gaps as 0).
+ *   forward   writes every element of feat [B, L nh + K nv] and, unless `arg` is NULL (inference), of arg.
+ *   backward  from gfeat [B, L nh + K nv], with feat and arg as the forward left them: writes every element of gx [B, L, K]
+ *             (gather form per (b, t, c), a fixed order) and gparams.  The horizontal gradient flows only through position arg
+ *             of a unit with feat > 0, the vertical one through units with feat > 0.  Parameter gradients are summed over
+ *             slabs of the batch as partials in `ws` (lr_caser_bwd_ws_bytes bytes, contents arbitrary on entry; the number of
+ *             slabs is capped, so the workspace does not grow with B beyond that) added in slab order.
+ * ---------------------------------------------------------------------------------- */
+int lr_caser_supported(int L, int K, int nh, int nv);
+size_t lr_caser_params_bytes(int L, int K, int nh, int nv);
+size_t lr_caser_bwd_ws_bytes(int64_t B, int L, int K, int nh, int nv);
+int lr_caser_fwd_f32(const float* table, int64_t V, const int32_t* ids, int64_t B, int L, int K, int nh, int nv,
+                     const float* params, float* feat, int32_t* arg, lr_stream_t stream);
+int lr_caser_bwd_f32(const float* table, int64_t V, const int32_t* ids, int64_t B, int L, int K, int nh, int nv,
+                     const float* params, const float* feat, const int32_t* arg, const float* gfeat, float* gx,
+                     float* gparams, void* ws, size_t ws_bytes, lr_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * AutoInt — the interaction stack of libreco/algorithms/autoint.py:146-168 (layers/attention.py:67-101, the Keras
  * MultiHeadAttention(use_bias=False) branch) and its Dense(1) read-out in one forward launch, f32 on the VALU.  T (fields), D
  * (embedding width) and H * head_dims[l] in [1, 64], H in [1, 8], 1 to 8 layers (lr_autoint_supported, otherwise LR_ESHAPE).

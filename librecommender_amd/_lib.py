@@ -241,6 +241,11 @@ SIGNATURES = {
     "lr_wavenet_bwd_ws_bytes": (_sz, [_i64, _int, _int, _int, _int, _int]),
     "lr_wavenet_fwd_f32": (_int, [_p, _i64, _p, _i64, _int, _int, _int, _int, _int, _p, _p, _sz, _p, _p, _p]),
     "lr_wavenet_bwd_f32": (_int, [_p, _i64, _p, _i64, _int, _int, _int, _int, _int, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "lr_caser_supported": (_int, [_int, _int, _int, _int]),
+    "lr_caser_params_bytes": (_sz, [_int, _int, _int, _int]),
+    "lr_caser_bwd_ws_bytes": (_sz, [_i64, _int, _int, _int, _int]),
+    "lr_caser_fwd_f32": (_int, [_p, _i64, _p, _i64, _int, _int, _int, _int, _p, _p, _p, _p]),
+    "lr_caser_bwd_f32": (_int, [_p, _i64, _p, _i64, _int, _int, _int, _int, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "lr_autoint_supported": (_int, [_int, _int, _int, _int, _p]),
     "lr_autoint_params_bytes": (_sz, [_int, _int, _int, _int, _p]),
     "lr_autoint_fwd_acts_bytes": (_sz, [_i64, _int, _int, _int]),

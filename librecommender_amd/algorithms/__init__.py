@@ -1,6 +1,7 @@
 from .als import ALS
 from .autoint import AutoInt
 from .bpr import BPR
+from .caser import Caser
 from .deepwalk import DeepWalk
 from .din import DIN
 from .fm import FM, DeepFM
@@ -20,4 +21,4 @@ from .wavenet import WaveNet
 from .youtube_ranking import YouTubeRanking
 from .youtube_retrieval import YouTubeRetrieval
 
-__all__ = ["ALS", "AutoInt", "BPR", "DIN", "DeepFM", "DeepWalk", "FM", "Item2Vec", "ItemCF", "LightGCN", "NGCF", "RNN4Rec", "SIM", "SVD", "SVDpp", "Swing", "Transformer", "TwoTower", "UserCF", "WaveNet", "YouTubeRanking", "YouTubeRetrieval"]
+__all__ = ["ALS", "AutoInt", "BPR", "Caser", "DIN", "DeepFM", "DeepWalk", "FM", "Item2Vec", "ItemCF", "LightGCN", "NGCF", "RNN4Rec", "SIM", "SVD", "SVDpp", "Swing", "Transformer", "TwoTower", "UserCF", "WaveNet", "YouTubeRanking", "YouTubeRetrieval"]

@@ -1,11 +1,11 @@
 """Embedding models whose user vector can be recomputed at serving time from a behaviour sequence and / or overridden user
-features (`libreco/bases/dyn_embed_base.py:17-322`): `RNN4Rec`, `WaveNet`, `YouTubeRetrieval`, `TwoTower`.  The id
+features (`libreco/bases/dyn_embed_base.py:17-322`): `RNN4Rec`, `WaveNet`, `Caser`, `YouTubeRetrieval`, `TwoTower`.  The id
 conversion, the dynamic branch of `recommend_user`, the sequence window, the user-feature override and the export tail of
 `set_embeddings` live here; a model supplies `dyn_user_embedding` (its one call into the net) and, if it takes sequences,
 `_default_window`.
 
 `SeqTowerCheckpoint` is the checkpoint surface of the models whose net is a `nets.seq_tower.SeqTowerNet` (`NamedTables` +
-`DenseParams`): `RNN4Rec` and `WaveNet`.
+`DenseParams`): `RNN4Rec`, `WaveNet` and `Caser`.
 """
 from __future__ import annotations
 

@@ -1,6 +1,7 @@
 """Device-side computation graphs of the north-star models (what `build_model()` creates in the
 reference), expressed over the HIP hot-path kernels + torch dense layers."""
 from .autoint_net import FeatAutoIntNet
+from .caser_net import CaserNet
 from .feat_embedding import FeatEmbedding, FeatSpec
 from .feat_nets import FeatDeepFMNet, FeatDINNet, FeatFMNet, FeatYouTubeRankingNet, ShardedDINNet
 from .field_parallel import FieldParallelDeepFMNet
@@ -11,4 +12,4 @@ from .wavenet_net import WaveNetNet
 from .tower_nets import ShardedTwoTowerNet, TwoTowerNet
 
 __all__ = ["DeepFMNet", "FMNet", "ShardedDeepFMNet", "ShardedFMNet", "FieldParallelDeepFMNet", "TwoTowerNet", "ShardedTwoTowerNet", "FeatEmbedding",
-           "FeatSpec", "FeatDeepFMNet", "FeatDINNet", "FeatFMNet", "FeatYouTubeRankingNet", "ShardedDINNet", "NGCFNet", "RNN4RecNet", "WaveNetNet", "FeatAutoIntNet"]
+           "FeatSpec", "FeatDeepFMNet", "FeatDINNet", "FeatFMNet", "FeatYouTubeRankingNet", "ShardedDINNet", "NGCFNet", "RNN4RecNet", "WaveNetNet", "FeatAutoIntNet", "CaserNet"]

@@ -1,4 +1,4 @@
-"""What the id-window towers (`nets/rnn_nets.py`, `nets/wavenet_net.py`) share: row tables `seq_embeds_var` (pad row
+"""What the id-window towers (`nets/rnn_nets.py`, `nets/wavenet_net.py`, `nets/caser_net.py`) share: row tables `seq_embeds_var` (pad row
 `n_items`), `item_embeds_var` and `item_bias_var` as `NamedTables`, a `DenseParams` for everything else, the pointwise losses
 against the item rows, and the TF1 Adam step of the tables from the window's and the batch's (id, gradient) streams.
 

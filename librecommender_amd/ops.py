@@ -2230,6 +2230,77 @@ def wavenet_bwd(table: torch.Tensor, ids: torch.Tensor, params: torch.Tensor, F:
 
 
 # --------------------------------------------------------------------------------------
+# Caser convolutions (csrc/caser.hip)
+# --------------------------------------------------------------------------------------
+def caser_supported(L: int, K: int, nh: int, nv: int) -> bool:
+    """Whether the Caser kernels take windows of `L` ids, a table of width `K`, `nh` horizontal and `nv` vertical filters."""
+    return bool(_lib.load().lr_caser_supported(int(L), int(K), int(nh), int(nv)))
+
+
+def caser_param_floats(L: int, K: int, nh: int, nv: int) -> int:
+    """Length of the parameter buffer (conv1d/kernel [1, K, nh], conv1d/bias, ... conv1d_{L-1}/kernel [L, K, nh] and bias, then
+    the vertical conv1d_{L}/kernel [1, L, nv] and bias, every tensor on a 16-byte boundary: the layout `DenseParams` gives
+    tensors added in that order); 0 for an unsupported shape."""
+    return _lib.load().lr_caser_params_bytes(int(L), int(K), int(nh), int(nv)) // 4
+
+
+def _caser_check(table, ids, params, nh, nv):
+    """-> (B, L, K, V) of one Caser call, its operands validated."""
+    K = _req(table, torch.float32, "table", 2).shape[1]
+    _req(ids, torch.int32, "ids", 2)
+    _req(params, torch.float32, "params", 1)
+    B, L = ids.shape
+    if table.shape[0] < 1:
+        raise ValueError("table must hold at least one row")
+    if not caser_supported(L, K, nh, nv):
+        raise ValueError(f"unsupported Caser shape: L={L}, K={K}, nh={nh}, nv={nv} (L from 1 to 64, K from 1 to 128, nh and nv "
+                         "from 1 to 64)")
+    if params.numel() != caser_param_floats(L, K, nh, nv):
+        raise ValueError("params must be the flat parameter buffer of this shape (see `caser_param_floats`)")
+    if params.data_ptr() % 16:
+        raise ValueError("params must start on a 16-byte boundary")
+    return B, L, K, table.shape[0]
+
+
+def caser_fwd(table: torch.Tensor, ids: torch.Tensor, params: torch.Tensor, nh: int, nv: int, need_arg: bool = True):
+    """`lr_caser_fwd_f32`: the L horizontal convolutions with their max over time and the vertical convolution over the rows
+    table[ids] read in place.  Returns (feat [B, L nh + K nv], arg int32 [B, L nh]: the first position that holds each
+    maximum; None unless `need_arg`, the inference mode)."""
+    B, L, K, V = _caser_check(table, ids, params, nh, nv)
+    dev = table.device
+    feat = torch.empty((max(B, 1), L * nh + K * nv), dtype=torch.float32, device=dev)[:B]
+    arg = torch.empty((max(B, 1), L * nh), dtype=torch.int32, device=dev)[:B] if need_arg else None
+    if B == 0:
+        return feat, arg
+    _call("lr_caser_fwd_f32", _ptr(table), V, _ptr(ids), B, L, K, nh, nv, _ptr(params), _ptr(feat), _ptr(arg), _stream())
+    return feat, arg
+
+
+def caser_bwd(table: torch.Tensor, ids: torch.Tensor, params: torch.Tensor, nh: int, nv: int, feat: torch.Tensor,
+              arg: torch.Tensor, gfeat: torch.Tensor, gparams: Optional[torch.Tensor] = None):
+    """`lr_caser_bwd_f32`: from gfeat [B, L nh + K nv] -> (gx [B, L, K], gparams in the layout of `params`); `gparams` may be
+    given (e.g. a slice of `DenseParams.grad`) and is overwritten.  Parameter gradients are summed in a fixed order."""
+    B, L, K, V = _caser_check(table, ids, params, nh, nv)
+    dev, width = table.device, L * nh + K * nv
+    if _req(feat, torch.float32, "feat", 2).shape != (B, width) or _req(gfeat, torch.float32, "gfeat", 2).shape != (B, width):
+        raise ValueError("feat and gfeat must be [B, L nh + K nv]")
+    if _req(arg, torch.int32, "arg", 2).shape != (B, L * nh):
+        raise ValueError("arg must be the forward's [B, L nh]")
+    if gparams is None:
+        gparams = torch.empty_like(params)
+    elif _req(gparams, torch.float32, "gparams", 1).numel() != params.numel():
+        raise ValueError("gparams must have the length of params")
+    gx = torch.empty((max(B, 1), L, K), dtype=torch.float32, device=dev)[:B]
+    if B == 0:
+        gparams.zero_()
+        return gx, gparams
+    ws = torch.empty(max(_lib.load().lr_caser_bwd_ws_bytes(B, L, K, nh, nv), 256), dtype=torch.uint8, device=dev)
+    _call("lr_caser_bwd_f32", _ptr(table), V, _ptr(ids), B, L, K, nh, nv, _ptr(params), _ptr(feat), _ptr(arg), _ptr(gfeat),
+          _ptr(gx), _ptr(gparams), _ptr(ws), ws.numel(), _stream())
+    return gx, gparams
+
+
+# --------------------------------------------------------------------------------------
 # AutoInt stack (csrc/autoint.hip)
 # --------------------------------------------------------------------------------------
 def _head_dims(head_dims):
