@@ -1255,6 +1255,70 @@ int lr_w2v_out_update_f32(float* table, int64_t V, int D, const int32_t* seg_pos
                           const int32_t* seg_start, const int32_t* n_seg, int64_t n, const float* g, const int32_t* slot_in,
                           const float* other, int64_t other_rows, lr_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * GraphSage: the neighbour sampling and the tower of libreco/algorithms/graphsage.py (sampling/random_walks.py,
+ * sampling/negatives.py, torch_modules/graphsage_module.py).  Every random choice is H(seed, stream, a, b) of the word2vec block
+ * above; an index below len is (hi32(H) * len) >> 32; integers are bit-exact against tests/sage_oracle.py.  The graph is two CSRs
+ * with int64 pointers and int32 indices, duplicates kept: item_ptr / item_idx the consumers of an item, user_ptr / user_idx the
+ * items of a user.  One walk from an item is a uniform consumer (half 0) and then a uniform item of that consumer (half 1); an
+ * item nobody consumed, or an id outside the graph, walks to itself.  No float atomics: same bits from run to run.
+ *   neighbors    out [n_nodes, num_neighbors] (1 .. 10).  Slot j of node i draws H(seed, 16, step * 8 + level, ((i * 16 + j) * 16 +
+ *                attempt) * 2 + half): attempt 0; if that is the node itself or one of its slots < j, attempts 1 .. 5 until neither
+ *                holds; then attempts 6 .. 10 until it is not the node itself; then attempt 11 stands.
+ *   pairs        walk w of start i (num_walks each, walk_len steps) draws H(seed, 17, step, (((i * num_walks + w) * walk_len) + s)
+ *                * 2 + half) and emits (cur, next) where next != cur, or with focus_start (start, next) where next != start; walk 0
+ *                of a start all of whose consumers hold one item emits (start, start) first.  offs == NULL counts per (start,
+ *                walk) into counts; otherwise offs is their exclusive scan and at most n_pairs pairs are written, in ascending
+ *                (start, walk, step).
+ *   starts       out[i] = (hi32(H(seed, 18, step, i)) * n_items) >> 32, or with cum [n_items] (a cumulative table scaled to 2^32)
+ *                the first item whose cum[] exceeds hi32(H).
+ *   negatives    out [n, num_neg]: slot q = i * num_neg + k draws H(seed, 19, step, q * 16 + attempt).  mode 0 (random): uniform,
+ *                redrawn up to 10 times while it equals items_pos[i] or items[i] (items may be NULL); mode 1 (popular): from cum,
+ *                redrawn once on that condition; mode 2 (out-batch): uniform, redrawn up to 10 times while in_batch[draw] != 0
+ *                (in_batch [n_items]).  The last draw stands.
+ *   dropout      keep [n_nodes, K]: hi32(H(seed, 20, step, (((node * 128 + column) * 2 + role) * 4 + level) * 4 + layer)) >=
+ *                floor(p * 2^32); role 0 the node itself, 1 the node as a neighbour; node counts inside its level of the batch.
+ *   fwd / bwd    B trees of levels 0 .. num_layers with num_neighbors^k nodes; rows / scale [B N, T] hold every node's T slots
+ *                (row of table [V, K], scale; scale NULL: all 1) level-major: level k starts at node B (1 + n + .. + n^(k-1)) and
+ *                tree b's nodes i n^k-wise at b n^k + i; node i of level k has the children i n .. i n + n - 1 of level k + 1.
+ *                params (lr_sage_params_bytes): proj W^T [T K, K], proj b [K], then per layer W^T [2 K, K], b [K].  h_0 =
+ *                proj(concat(scale * row)); layer l: h[v] = act(W [drop(h[v]); mean_children drop(h[child])] + b) over levels 0 ..
+ *                L - l - 1, ReLU on all but the last layer; repr [B, K] = level 0 after the last layer.  Every element is one fmaf
+ *                chain (bias, inputs ascending).  train == 0 or dropout == 0 draws nothing.  bwd recomputes the activations from
+ *                the same arguments and writes grow [B N, T, K] (the slot-row gradients times the slot's scale, exactly 0 for a row
+ *                outside [0, V)), gparams (the layout of params) and, unless NULL, relu_out: per ReLU layer l a block
+ *                [B, nodes with an output in layer l, K] of 0 / 1.  ws holds lr_sage_bwd_ws_bytes: lr_sage_bwd_slabs slabs of
+ *                partials, added in slab order.  Shapes: lr_sage_supported (K 1 .. 64, T 1 .. 16, num_layers 0 .. 3,
+ *                num_neighbors 1 .. 10 with num_neighbors^num_layers <= 100), otherwise LR_ESHAPE.
+ * ---------------------------------------------------------------------------------- */
+int lr_sage_supported(int K, int T, int num_layers, int num_neighbors);
+size_t lr_sage_params_bytes(int K, int T, int num_layers);
+int lr_sage_bwd_slabs(int64_t B, int K, int T, int num_layers, int num_neighbors);
+size_t lr_sage_bwd_ws_bytes(int64_t B, int K, int T, int num_layers, int num_neighbors);
+int lr_sage_neighbors_i32(const int32_t* nodes, int64_t n_nodes, int num_neighbors, const int64_t* item_ptr,
+                          const int32_t* item_idx, int64_t n_items, int64_t n_item_idx, const int64_t* user_ptr,
+                          const int32_t* user_idx, int64_t n_users, int64_t n_user_idx, uint64_t seed, int64_t step, int level,
+                          int32_t* out, lr_stream_t stream);
+int lr_sage_pairs_i32(const int32_t* starts, int64_t n_starts, int num_walks, int walk_len, int focus_start,
+                      const int64_t* item_ptr, const int32_t* item_idx, int64_t n_items, int64_t n_item_idx,
+                      const int64_t* user_ptr, const int32_t* user_idx, int64_t n_users, int64_t n_user_idx, uint64_t seed,
+                      int64_t step, int32_t* counts, const int64_t* offs, int64_t n_pairs, int32_t* items, int32_t* items_pos,
+                      lr_stream_t stream);
+int lr_sage_starts_i32(int64_t n, int64_t n_items, const int64_t* cum, uint64_t seed, int64_t step, int32_t* out,
+                       lr_stream_t stream);
+int lr_sage_negatives_i32(const int32_t* items, const int32_t* items_pos, int64_t n, int num_neg, int64_t n_items, int mode,
+                          const int64_t* cum, const uint8_t* in_batch, uint64_t seed, int64_t step, int32_t* out,
+                          lr_stream_t stream);
+int lr_sage_dropout_u8(int64_t n_nodes, int K, double p, uint64_t seed, int64_t step, int layer, int level, int role,
+                       uint8_t* keep, lr_stream_t stream);
+int lr_sage_fwd_f32(const float* table, int64_t V, const int32_t* rows, const float* scale, int64_t B, int K, int T,
+                    int num_layers, int num_neighbors, const float* params, double dropout, uint64_t seed, int64_t step,
+                    int train, float* repr, lr_stream_t stream);
+int lr_sage_bwd_f32(const float* table, int64_t V, const int32_t* rows, const float* scale, int64_t B, int K, int T,
+                    int num_layers, int num_neighbors, const float* params, double dropout, uint64_t seed, int64_t step,
+                    const float* grepr, float* grow, float* gparams, uint8_t* relu_out, void* ws, size_t ws_bytes,
+                    lr_stream_t stream);
+
 /* Measurement probe (scripts/mfma_peak.py): iters x 8 back-to-back v_mfma_f32_32x32x2_f32 per wave on
  * 256 x waves_per_simd workgroups — the f32 MFMA rate the chip sustains at the clock it holds under that load. */
 int lr_mfma_f32_probe(int iters, int waves_per_simd, float* out, lr_stream_t stream);

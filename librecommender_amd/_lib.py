@@ -263,6 +263,19 @@ SIGNATURES = {
     "lr_w2v_score_f32": (_int, [_p, _i64, _p, _i64, _int, _p, _p, _i64, _p, _p, _p, _i64, C.c_double, C.c_double, _p, _p, _p,
                                 _p]),
     "lr_w2v_out_update_f32": (_int, [_p, _i64, _int, _p, _p, _p, _p, _i64, _p, _p, _p, _i64, _p]),
+    "lr_sage_supported": (_int, [_int, _int, _int, _int]),
+    "lr_sage_params_bytes": (_sz, [_int, _int, _int]),
+    "lr_sage_bwd_slabs": (_int, [_i64, _int, _int, _int, _int]),
+    "lr_sage_bwd_ws_bytes": (_sz, [_i64, _int, _int, _int, _int]),
+    "lr_sage_neighbors_i32": (_int, [_p, _i64, _int, _p, _p, _i64, _i64, _p, _p, _i64, _i64, C.c_uint64, _i64, _int, _p, _p]),
+    "lr_sage_pairs_i32": (_int, [_p, _i64, _int, _int, _int, _p, _p, _i64, _i64, _p, _p, _i64, _i64, C.c_uint64, _i64, _p, _p,
+                                 _i64, _p, _p, _p]),
+    "lr_sage_starts_i32": (_int, [_i64, _i64, _p, C.c_uint64, _i64, _p, _p]),
+    "lr_sage_negatives_i32": (_int, [_p, _p, _i64, _int, _i64, _int, _p, _p, C.c_uint64, _i64, _p, _p]),
+    "lr_sage_dropout_u8": (_int, [_i64, _int, C.c_double, C.c_uint64, _i64, _int, _int, _int, _p, _p]),
+    "lr_sage_fwd_f32": (_int, [_p, _i64, _p, _p, _i64, _int, _int, _int, _int, _p, C.c_double, C.c_uint64, _i64, _int, _p, _p]),
+    "lr_sage_bwd_f32": (_int, [_p, _i64, _p, _p, _i64, _int, _int, _int, _int, _p, C.c_double, C.c_uint64, _i64, _p, _p, _p, _p,
+                               _p, _sz, _p]),
 }
 
 _lib = None

@@ -5,6 +5,7 @@ from .caser import Caser
 from .deepwalk import DeepWalk
 from .din import DIN
 from .fm import FM, DeepFM
+from .graphsage import GraphSage
 from .item2vec import Item2Vec
 from .item_cf import ItemCF
 from .lightgcn import LightGCN
@@ -21,4 +22,4 @@ from .wavenet import WaveNet
 from .youtube_ranking import YouTubeRanking
 from .youtube_retrieval import YouTubeRetrieval
 
-__all__ = ["ALS", "AutoInt", "BPR", "Caser", "DIN", "DeepFM", "DeepWalk", "FM", "Item2Vec", "ItemCF", "LightGCN", "NGCF", "RNN4Rec", "SIM", "SVD", "SVDpp", "Swing", "Transformer", "TwoTower", "UserCF", "WaveNet", "YouTubeRanking", "YouTubeRetrieval"]
+__all__ = ["ALS", "AutoInt", "BPR", "Caser", "DIN", "DeepFM", "DeepWalk", "FM", "GraphSage", "Item2Vec", "ItemCF", "LightGCN", "NGCF", "RNN4Rec", "SIM", "SVD", "SVDpp", "Swing", "Transformer", "TwoTower", "UserCF", "WaveNet", "YouTubeRanking", "YouTubeRetrieval"]

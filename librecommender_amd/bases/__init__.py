@@ -4,7 +4,8 @@ from .embed_base import EmbedBase
 from .dyn_embed_base import DynEmbedBase
 from .feat_base import FeatBase
 from .word2vec_base import Word2VecBase
+from .sage_base import SageBase
 
 GensimBase = Word2VecBase      # the reference's name for this base
 
-__all__ = ["Base", "CfBase", "EmbedBase", "DynEmbedBase", "FeatBase", "Word2VecBase", "GensimBase"]
+__all__ = ["Base", "CfBase", "EmbedBase", "DynEmbedBase", "FeatBase", "Word2VecBase", "GensimBase", "SageBase"]

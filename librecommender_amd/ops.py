@@ -2537,3 +2537,174 @@ def w2v_out_update(table: torch.Tensor, seg: Segments, other: torch.Tensor, g: O
         raise ValueError("shape mismatch")
     _call("lr_w2v_out_update_f32", _ptr(table), V, D, _ptr(seg.pos), _ptr(seg.rows), _ptr(seg.start), _ptr(seg.n_seg), seg.n,
           _ptr(g), _ptr(slot_in), _ptr(other), other.shape[0], _stream())
+
+
+# --------------------------------------------------------------------------------------
+# GraphSage: neighbour sampling and the fused tower (csrc/sage.hip)
+# --------------------------------------------------------------------------------------
+SAGE_NEG_MODES = {"random": 0, "popular": 1, "out-batch": 2}
+
+
+@dataclass
+class SageGraph:
+    """The two CSRs of the bipartite graph on the device (int64 pointers, int32 indices, duplicates kept)."""
+
+    item_ptr: torch.Tensor     # [n_items + 1]: the consumers of an item
+    item_idx: torch.Tensor
+    user_ptr: torch.Tensor     # [n_users + 1]: the items of a user
+    user_idx: torch.Tensor
+
+    def __post_init__(self):
+        _req(self.item_ptr, torch.int64, "item_ptr", 1)
+        _req(self.item_idx, torch.int32, "item_idx", 1)
+        _req(self.user_ptr, torch.int64, "user_ptr", 1)
+        _req(self.user_idx, torch.int32, "user_idx", 1)
+        if self.item_ptr.numel() < 2 or self.user_ptr.numel() < 2:
+            raise ValueError("the graph needs at least one item and one user")
+
+    def args(self):
+        return (_ptr(self.item_ptr), _ptr(self.item_idx), self.item_ptr.numel() - 1, self.item_idx.numel(), _ptr(self.user_ptr),
+                _ptr(self.user_idx), self.user_ptr.numel() - 1, self.user_idx.numel())
+
+
+def sage_supported(K: int, T: int, num_layers: int, num_neighbors: int) -> bool:
+    """`lr_sage_supported`: whether the fused tower takes this shape."""
+    return bool(_lib.load().lr_sage_supported(int(K), int(T), int(num_layers), int(num_neighbors)))
+
+
+def sage_param_floats(K: int, T: int, num_layers: int) -> int:
+    """Length of the parameter pack: proj W^T [T K, K], proj b [K], then per layer W^T [2 K, K], b [K] (0: unsupported)."""
+    return _lib.load().lr_sage_params_bytes(int(K), int(T), int(num_layers)) // 4
+
+
+def sage_bwd_slabs(B: int, K: int, T: int, num_layers: int, num_neighbors: int) -> int:
+    return int(_lib.load().lr_sage_bwd_slabs(int(B), int(K), int(T), int(num_layers), int(num_neighbors)))
+
+
+def sage_neighbors(nodes: torch.Tensor, graph: SageGraph, num_neighbors: int, seed: int, step: int, level: int) -> torch.Tensor:
+    """`lr_sage_neighbors_i32`: int32 [n_nodes, num_neighbors], the sampled neighbours of one level of nodes."""
+    _req(nodes, torch.int32, "nodes", 1)
+    if not 1 <= int(num_neighbors) <= 10:
+        raise ValueError("`num_neighbors` must be from 1 to 10")
+    n = nodes.numel()
+    out = torch.empty((max(n, 1), int(num_neighbors)), dtype=torch.int32, device=nodes.device)[:n]
+    _call("lr_sage_neighbors_i32", _ptr(nodes), n, int(num_neighbors), *graph.args(), int(seed) & _U64, int(step), int(level),
+          _ptr(out), _stream())
+    return out
+
+
+def sage_pairs(starts: torch.Tensor, graph: SageGraph, num_walks: int, walk_len: int, focus_start: bool, seed: int, step: int):
+    """`lr_sage_pairs_i32` (count, a torch scan, emit) -> (items, items_pos) int32 [n_pairs] in ascending (start, walk, step).
+    The pair count is read back once."""
+    _req(starts, torch.int32, "starts", 1)
+    if num_walks < 1 or walk_len < 1:
+        raise ValueError("`num_walks` and `sample_walk_len` must be at least 1")
+    n, dev = starts.numel(), starts.device
+    head = (_ptr(starts), n, int(num_walks), int(walk_len), 1 if focus_start else 0, *graph.args(), int(seed) & _U64, int(step))
+    counts = torch.empty(max(n * num_walks, 1), dtype=torch.int32, device=dev)[:n * num_walks]
+    _call("lr_sage_pairs_i32", *head, _ptr(counts), None, 0, None, None, _stream())
+    incl = torch.cumsum(counts, 0, dtype=torch.int64)
+    n_pairs = int(incl[-1].item()) if n else 0
+    offs = (incl - counts).contiguous()
+    items, items_pos = (torch.empty(max(n_pairs, 1), dtype=torch.int32, device=dev)[:n_pairs] for _ in range(2))
+    _call("lr_sage_pairs_i32", *head, None, _ptr(offs), n_pairs, _ptr(items), _ptr(items_pos), _stream())
+    return items, items_pos
+
+
+def sage_starts(n: int, n_items: int, seed: int, step: int, device, cum: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`lr_sage_starts_i32`: n start nodes, uniform or (with `cum` int64 [n_items]) from the cumulative table."""
+    if cum is not None and _req(cum, torch.int64, "cum", 1).numel() != int(n_items):
+        raise ValueError("cum must hold n_items entries")
+    out = torch.empty(max(int(n), 1), dtype=torch.int32, device=device)[:int(n)]
+    _call("lr_sage_starts_i32", int(n), int(n_items), _ptr(cum), int(seed) & _U64, int(step), _ptr(out), _stream())
+    return out
+
+
+def sage_negatives(items: Optional[torch.Tensor], items_pos: torch.Tensor, num_neg: int, n_items: int, mode: str, seed: int,
+                   step: int, cum: Optional[torch.Tensor] = None, in_batch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`lr_sage_negatives_i32`: int32 [n * num_neg]; `mode` is "random", "popular" (needs `cum`) or "out-batch" (needs
+    `in_batch` uint8 [n_items])."""
+    _req(items_pos, torch.int32, "items_pos", 1)
+    n = items_pos.numel()
+    if items is not None and _req(items, torch.int32, "items", 1).numel() != n:
+        raise ValueError("items and items_pos must have the same length")
+    if mode not in SAGE_NEG_MODES:
+        raise ValueError(f"unknown negative mode: {mode}")
+    if mode == "popular" and (cum is None or _req(cum, torch.int64, "cum", 1).numel() != int(n_items)):
+        raise ValueError("`popular` needs cum int64 [n_items]")
+    if mode == "out-batch" and (in_batch is None or _req(in_batch, torch.uint8, "in_batch", 1).numel() != int(n_items)):
+        raise ValueError("`out-batch` needs in_batch uint8 [n_items]")
+    if num_neg < 1:
+        raise ValueError("`num_neg` must be at least 1")
+    out = torch.empty(max(n * int(num_neg), 1), dtype=torch.int32, device=items_pos.device)[:n * int(num_neg)]
+    _call("lr_sage_negatives_i32", _ptr(items), _ptr(items_pos), n, int(num_neg), int(n_items), SAGE_NEG_MODES[mode], _ptr(cum),
+          _ptr(in_batch), int(seed) & _U64, int(step), _ptr(out), _stream())
+    return out
+
+
+def sage_dropout_mask(n_nodes: int, K: int, p: float, seed: int, step: int, layer: int, level: int, role: int, device):
+    """`lr_sage_dropout_u8`: the keep flags uint8 [n_nodes, K] of one (layer, level, role)."""
+    if not 0.0 <= float(p) < 1.0:
+        raise ValueError("`dropout_rate` must be in [0, 1)")
+    keep = torch.empty((max(int(n_nodes), 1), int(K)), dtype=torch.uint8, device=device)[:int(n_nodes)]
+    _call("lr_sage_dropout_u8", int(n_nodes), int(K), float(p), int(seed) & _U64, int(step), int(layer), int(level), int(role),
+          _ptr(keep), _stream())
+    return keep
+
+
+def sage_tree_nodes(num_layers: int, num_neighbors: int) -> int:
+    return sum(int(num_neighbors) ** k for k in range(int(num_layers) + 1)) if num_layers > 0 else 1
+
+
+def _sage_check(table, rows, scale, params, num_layers, num_neighbors, dropout):
+    _req(table, torch.float32, "table", 2)
+    _req(rows, torch.int32, "rows", 2)
+    _req(params, torch.float32, "params", 1)
+    V, K = table.shape
+    T = rows.shape[1]
+    N = sage_tree_nodes(num_layers, num_neighbors)
+    if not sage_supported(K, T, num_layers, num_neighbors):
+        raise ValueError(f"unsupported GraphSage shape: K={K} T={T} num_layers={num_layers} num_neighbors={num_neighbors} "
+                         "(see `sage_supported`)")
+    if rows.shape[0] % N:
+        raise ValueError(f"rows must hold a whole number of trees of {N} nodes")
+    if scale is not None and _req(scale, torch.float32, "scale", 2).shape != rows.shape:
+        raise ValueError("scale must have the shape of rows")
+    if params.numel() != sage_param_floats(K, T, num_layers):
+        raise ValueError("params must be the parameter pack of this shape (see `sage_param_floats`)")
+    if not 0.0 <= float(dropout) < 1.0:
+        raise ValueError("`dropout_rate` must be in [0, 1)")
+    return rows.shape[0] // N, K, T, V
+
+
+def sage_fwd(table: torch.Tensor, rows: torch.Tensor, scale: Optional[torch.Tensor], params: torch.Tensor, num_layers: int,
+             num_neighbors: int, dropout: float = 0.0, seed: int = 0, step: int = 0, train: bool = False) -> torch.Tensor:
+    """`lr_sage_fwd_f32`: repr [B, K] of B trees whose slots `rows` / `scale` [B N, T] are laid out level-major (see the
+    header).  `train=False` is the inference mode: no dropout is drawn."""
+    B, K, T, V = _sage_check(table, rows, scale, params, num_layers, num_neighbors, dropout)
+    repr_ = torch.empty((max(B, 1), K), dtype=torch.float32, device=table.device)[:B]
+    _call("lr_sage_fwd_f32", _ptr(table), V, _ptr(rows), _ptr(scale), B, K, T, int(num_layers), int(num_neighbors), _ptr(params),
+          float(dropout), int(seed) & _U64, int(step), 1 if train else 0, _ptr(repr_), _stream())
+    return repr_
+
+
+def sage_bwd(table: torch.Tensor, rows: torch.Tensor, scale: Optional[torch.Tensor], params: torch.Tensor, num_layers: int,
+             num_neighbors: int, grepr: torch.Tensor, dropout: float = 0.0, seed: int = 0, step: int = 0,
+             want_relu: bool = False):
+    """`lr_sage_bwd_f32` -> (grow [B N, T, K], gparams in the layout of `params`, relu flags uint8 or None)."""
+    B, K, T, V = _sage_check(table, rows, scale, params, num_layers, num_neighbors, dropout)
+    _req(grepr, torch.float32, "grepr", 2)
+    if grepr.shape != (B, K):
+        raise ValueError("grepr must be [B, K]")
+    dev = table.device
+    n, L = int(num_neighbors), int(num_layers)
+    grow = torch.empty((max(rows.shape[0], 1), T, K), dtype=torch.float32, device=dev)[:rows.shape[0]]
+    gparams = torch.empty(params.numel(), dtype=torch.float32, device=dev)
+    relu = None
+    if want_relu:
+        n_relu = sum(sage_tree_nodes(L - l - 1, n) for l in range(L - 1))
+        relu = torch.empty((max(B * n_relu, 1), K), dtype=torch.uint8, device=dev)[:B * n_relu]
+    ws = torch.empty(max(_lib.load().lr_sage_bwd_ws_bytes(B, K, T, L, n), 256), dtype=torch.uint8, device=dev)
+    _call("lr_sage_bwd_f32", _ptr(table), V, _ptr(rows), _ptr(scale), B, K, T, L, n, _ptr(params), float(dropout),
+          int(seed) & _U64, int(step), _ptr(grepr), _ptr(grow), _ptr(gparams), _ptr(relu), _ptr(ws), ws.numel(), _stream())
+    return grow, gparams, relu
