@@ -1319,6 +1319,55 @@ int lr_sage_bwd_f32(const float* table, int64_t V, const int32_t* rows, const fl
                     const float* grepr, float* grow, float* gparams, uint8_t* relu_out, void* ws, size_t ws_bytes,
                     lr_stream_t stream);
 
+/* ----------------------------------------------------------------------------------
+ * PinSage: the importance-walk neighbour sampling and the tower of libreco/algorithms/pinsage.py
+ * (sampling/random_walks.py, graph/neighbor_walk.py, torch_modules/pinsage_module.py).  The graph, H, the one-walk rule, the
+ * trees, the slots and the level-major layout are those of the GraphSage block above; integers are bit-exact against
+ * tests/pinsage_oracle.py.  No float atomics: same bits from run to run.
+ *   neighbors    ids / counts [n_nodes, num_neighbors] (1 .. 10; num_walks * walk_len <= 64, otherwise LR_ESHAPE).  Node i of
+ *                the level runs num_walks walks of at most walk_len steps; step s of walk w draws H(seed, 21, step * 8 + level,
+ *                (i * 64 + w * walk_len + s) * 4 + kind), kind 0 the consumer, 1 the item, 2 the continue draw.  Step 0 is always
+ *                taken; before a later step the walk continues iff hi32(H) >= floor(termination_prob * 2^32), compared in 64
+ *                bits (>= 1: never, 0: always).  The visited items in ascending (walk, step) lose every occurrence of the node
+ *                itself, unless nothing else was visited, in which case one stays; then, where tree_exclude != NULL,
+ *                tree_exclude[b] >= 0 and the node equals tree_target[b] for its tree b = i / num_neighbors^level, every
+ *                occurrence of tree_exclude[b] by the same rule (tree_target / tree_exclude [n_trees], n_nodes == n_trees *
+ *                num_neighbors^level).  The num_neighbors most visited items follow in descending count, ties by first visit,
+ *                with their counts; unused slots hold id -1 and count 0.  A node all of whose consumers hold one item, an item
+ *                nobody consumed and an id outside the graph give themselves with count 1.
+ *   fwd / bwd    the arguments of lr_sage_fwd_f32 / lr_sage_bwd_f32 and weights [B (N - 1)]: the importance weight of every
+ *                node of the levels 1 .. num_layers, at the node's position in the level-major arrays minus B (may be NULL
+ *                when num_layers == 0).  params (lr_pinsage_params_bytes): proj W^T [T K, K], proj b [K]; per layer Q^T [K, K],
+ *                bq [K], W^T [2 K, K], bw [K]; the head G1^T [K, K], b1 [K], G2^T [K, K].  Layer l over the levels k < L - l:
+ *                nb = drop(relu(Q h[child] + bq)) (the flags of lr_sage_dropout_u8 with role 1, layer l, level k + 1), agg =
+ *                sum_j w_j nb_j in child order with a child of weight 0 skipped, z = relu(W [h[v]; agg] + bw), h'[v] = z / |z|
+ *                with a norm of exactly 0 replaced by 1; repr [B, K] = G2 relu(G1 h[0] + b1).  Every element is one fma chain
+ *                (bias, inputs ascending) accumulated in f64 and rounded to f32 once, |z|^2 likewise over the columns: a target
+ *                has the same bits alone and in any batch.  bwd recomputes the activations and writes grow [B N, T, K] (times the slot's scale, exactly 0
+ *                for a row outside [0, V)), gparams (the layout of params) and, unless NULL, relu_out: per layer l a block
+ *                [B, n_l - 1, K] of the q flags (the nodes 1 .. n_l - 1 of a tree, n_l the nodes of the levels 0 .. L - l) and a
+ *                block [B, m_l, K] of the w flags (m_l the nodes of the levels 0 .. L - l - 1), then the head's flags [B, K].
+ *                ws holds lr_pinsage_bwd_ws_bytes: lr_pinsage_bwd_slabs slabs of partials, added in slab order in f64.  Shapes:
+ *                lr_pinsage_supported (K 1 .. 64, T 1 .. 16, num_layers 0 .. 3, num_neighbors 1 .. 10 with
+ *                num_neighbors^num_layers <= 100: one tree's backward image then fits in 96 KB of LDS), otherwise LR_ESHAPE.
+ * ---------------------------------------------------------------------------------- */
+int lr_pinsage_supported(int K, int T, int num_layers, int num_neighbors);
+size_t lr_pinsage_params_bytes(int K, int T, int num_layers);
+int lr_pinsage_bwd_slabs(int64_t B, int K, int T, int num_layers, int num_neighbors);
+size_t lr_pinsage_bwd_ws_bytes(int64_t B, int K, int T, int num_layers, int num_neighbors);
+int lr_pinsage_neighbors_i32(const int32_t* nodes, int64_t n_nodes, int num_neighbors, int num_walks, int walk_len,
+                             double termination_prob, const int32_t* tree_target, const int32_t* tree_exclude, int64_t n_trees,
+                             const int64_t* item_ptr, const int32_t* item_idx, int64_t n_items, int64_t n_item_idx,
+                             const int64_t* user_ptr, const int32_t* user_idx, int64_t n_users, int64_t n_user_idx, uint64_t seed,
+                             int64_t step, int level, int32_t* ids, int32_t* counts, lr_stream_t stream);
+int lr_pinsage_fwd_f32(const float* table, int64_t V, const int32_t* rows, const float* scale, const float* weights, int64_t B,
+                       int K, int T, int num_layers, int num_neighbors, const float* params, double dropout, uint64_t seed,
+                       int64_t step, int train, float* repr, lr_stream_t stream);
+int lr_pinsage_bwd_f32(const float* table, int64_t V, const int32_t* rows, const float* scale, const float* weights, int64_t B,
+                       int K, int T, int num_layers, int num_neighbors, const float* params, double dropout, uint64_t seed,
+                       int64_t step, const float* grepr, float* grow, float* gparams, uint8_t* relu_out, void* ws,
+                       size_t ws_bytes, lr_stream_t stream);
+
 /* Measurement probe (scripts/mfma_peak.py): iters x 8 back-to-back v_mfma_f32_32x32x2_f32 per wave on
  * 256 x waves_per_simd workgroups — the f32 MFMA rate the chip sustains at the clock it holds under that load. */
 int lr_mfma_f32_probe(int iters, int waves_per_simd, float* out, lr_stream_t stream);

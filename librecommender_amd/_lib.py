@@ -276,6 +276,16 @@ SIGNATURES = {
     "lr_sage_fwd_f32": (_int, [_p, _i64, _p, _p, _i64, _int, _int, _int, _int, _p, C.c_double, C.c_uint64, _i64, _int, _p, _p]),
     "lr_sage_bwd_f32": (_int, [_p, _i64, _p, _p, _i64, _int, _int, _int, _int, _p, C.c_double, C.c_uint64, _i64, _p, _p, _p, _p,
                                _p, _sz, _p]),
+    "lr_pinsage_supported": (_int, [_int, _int, _int, _int]),
+    "lr_pinsage_params_bytes": (_sz, [_int, _int, _int]),
+    "lr_pinsage_bwd_slabs": (_int, [_i64, _int, _int, _int, _int]),
+    "lr_pinsage_bwd_ws_bytes": (_sz, [_i64, _int, _int, _int, _int]),
+    "lr_pinsage_neighbors_i32": (_int, [_p, _i64, _int, _int, _int, C.c_double, _p, _p, _i64, _p, _p, _i64, _i64, _p, _p, _i64, _i64,
+                                        C.c_uint64, _i64, _int, _p, _p, _p]),
+    "lr_pinsage_fwd_f32": (_int, [_p, _i64, _p, _p, _p, _i64, _int, _int, _int, _int, _p, C.c_double, C.c_uint64, _i64, _int, _p,
+                                  _p]),
+    "lr_pinsage_bwd_f32": (_int, [_p, _i64, _p, _p, _p, _i64, _int, _int, _int, _int, _p, C.c_double, C.c_uint64, _i64, _p, _p, _p,
+                                  _p, _p, _sz, _p]),
 }
 
 _lib = None

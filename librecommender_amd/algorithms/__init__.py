@@ -10,6 +10,7 @@ from .item2vec import Item2Vec
 from .item_cf import ItemCF
 from .lightgcn import LightGCN
 from .ngcf import NGCF
+from .pinsage import PinSage
 from .rnn4rec import RNN4Rec
 from .sim import SIM
 from .svd import SVD
@@ -22,4 +23,4 @@ from .wavenet import WaveNet
 from .youtube_ranking import YouTubeRanking
 from .youtube_retrieval import YouTubeRetrieval
 
-__all__ = ["ALS", "AutoInt", "BPR", "Caser", "DIN", "DeepFM", "DeepWalk", "FM", "GraphSage", "Item2Vec", "ItemCF", "LightGCN", "NGCF", "RNN4Rec", "SIM", "SVD", "SVDpp", "Swing", "Transformer", "TwoTower", "UserCF", "WaveNet", "YouTubeRanking", "YouTubeRetrieval"]
+__all__ = ["ALS", "AutoInt", "BPR", "Caser", "DIN", "DeepFM", "DeepWalk", "FM", "GraphSage", "Item2Vec", "ItemCF", "LightGCN", "NGCF", "PinSage", "RNN4Rec", "SIM", "SVD", "SVDpp", "Swing", "Transformer", "TwoTower", "UserCF", "WaveNet", "YouTubeRanking", "YouTubeRetrieval"]

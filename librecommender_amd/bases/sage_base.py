@@ -2,8 +2,8 @@
 host (`graph/neighbor_walk.py`, `sampling/random_walks.py`, `batch/collators.py:322-396`: Python `random` per sampled
 neighbour and per walk step); here start nodes, walk pairs, negatives, neighbours and the whole tower run on the device
 (csrc/sage.hip, nets/sage_net.py).  Every draw is a function of (seed, global step, coordinates): two runs
-give the same bits.  `remove_edges` and `full_inference` are accepted and have no effect (the reference's non-DGL GraphSage
-never reads them)."""
+give the same bits.  `full_inference` is accepted and has no effect; `remove_edges` is read by PinSage's net under i2i only (the
+reference's non-DGL GraphSage never reads either).  A subclass names its net through `net_class`."""
 from __future__ import annotations
 
 import math
@@ -95,9 +95,14 @@ class SageBase(EmbedBase):
             user_sparse=d.user_sparse_unique if u2i else None, user_dense=d.user_dense_unique if u2i else None,
             user_dense_cols=list(d.user_dense_col.index))
 
-    def build_model(self):
+    def net_class(self):
+        """The net of the model and its keyword arguments beyond `SageNet`'s (a subclass with another tower overrides it)."""
         from ..nets.sage_net import SageNet
 
+        return SageNet, {}
+
+    def build_model(self):
+        SageNet, extra = self.net_class()
         self._check_trainer_params()
         self.device = hip_device(self._device_arg)
         kw = self.net_kwargs()
@@ -108,7 +113,7 @@ class SageBase(EmbedBase):
                              f"{self.num_neighbors} and {self.embed_size}")
         self.net = SageNet(self.paradigm, self.n_users, self.n_items, self.embed_size, self.num_layers, self.num_neighbors,
                            self.dropout_rate, self.device, self.sage_graph(), seed=self.seed, lr=self.lr, epsilon=self.epsilon,
-                           reg=self.reg, amsgrad=self.amsgrad, margin=self.margin, fused=self.fused, **kw)
+                           reg=self.reg, amsgrad=self.amsgrad, margin=self.margin, fused=self.fused, **kw, **extra)
         self._sampling_tables()
 
     def train_on_batch(self, batch):

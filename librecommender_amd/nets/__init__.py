@@ -9,8 +9,9 @@ from .fm_nets import DeepFMNet, FMNet, ShardedDeepFMNet, ShardedFMNet
 from .ngcf_net import NGCFNet
 from .rnn_nets import RNN4RecNet
 from .sage_net import SageNet
+from .pinsage_net import PinSageNet
 from .wavenet_net import WaveNetNet
 from .tower_nets import ShardedTwoTowerNet, TwoTowerNet
 
 __all__ = ["DeepFMNet", "FMNet", "ShardedDeepFMNet", "ShardedFMNet", "FieldParallelDeepFMNet", "TwoTowerNet", "ShardedTwoTowerNet", "FeatEmbedding",
-           "FeatSpec", "FeatDeepFMNet", "FeatDINNet", "FeatFMNet", "FeatYouTubeRankingNet", "ShardedDINNet", "NGCFNet", "RNN4RecNet", "WaveNetNet", "FeatAutoIntNet", "CaserNet", "SageNet"]
+           "FeatSpec", "FeatDeepFMNet", "FeatDINNet", "FeatFMNet", "FeatYouTubeRankingNet", "ShardedDINNet", "NGCFNet", "RNN4RecNet", "WaveNetNet", "FeatAutoIntNet", "CaserNet", "SageNet", "PinSageNet"]

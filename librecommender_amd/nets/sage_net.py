@@ -106,6 +106,7 @@ class SageNet:
         self.L, self.n, self.dropout = int(num_layers), int(num_neighbors), float(dropout_rate or 0.0)
         self.device, self.graph, self.seed = device, graph, int(seed)
         self.lr, self.epsilon, self.reg, self.margin = lr, epsilon, float(reg or 0.0), margin
+        self._want_fused = bool(fused)
         K, rng = self.K, np.random.default_rng(seed)
         u2i = paradigm == "u2i"
         # the stacked table
@@ -117,7 +118,17 @@ class SageNet:
         self.items = _Side(n_items, self.item_off, item_sparse, self.sparse_off, item_dense, item_dense_cols, self.dense_off, device)
         self.users = (_Side(n_users, self.user_off, user_sparse, self.sparse_off, user_dense, user_dense_cols, self.dense_off,
                             device) if u2i else None)
-        # the parameter packs
+        self._init_packs(rng, u2i)
+        self.m, self.v = torch.zeros_like(self.E), torch.zeros_like(self.E)
+        self.pm, self.pv = torch.zeros_like(self.P), torch.zeros_like(self.P)
+        self.vmax = torch.zeros_like(self.E) if amsgrad else None
+        self.pvmax = torch.zeros_like(self.P) if amsgrad else None
+        self._row_slot = torch.full((self.E.shape[0],), -1, dtype=torch.int32, device=device)
+        self.step = 0
+
+    def _init_packs(self, rng, u2i):
+        """The parameter packs `P`, their slices and whether each tower runs fused (a subclass with other towers overrides it)."""
+        K, device = self.K, self.device
         Ti = self.items.T
         relu_gain = math.sqrt(2.0)
         pack = [xavier_uniform(rng, K, Ti * K).T.reshape(-1), np.zeros(K, dtype=np.float32)]
@@ -131,14 +142,8 @@ class SageNet:
             pack += [xavier_uniform(rng, K, Tu * K).T.reshape(-1), np.zeros(K, dtype=np.float32)]
             self.user_pack = slice(n_item_pack, n_item_pack + Tu * K * K + K)
         self.P = torch.from_numpy(np.concatenate(pack).astype(np.float32)).to(device).contiguous()
-        self.item_fused = bool(fused) and ops.sage_supported(K, Ti, self.L, self.n)
-        self.user_fused = bool(fused) and u2i and ops.sage_supported(K, self.users.T, 0, 1)
-        self.m, self.v = torch.zeros_like(self.E), torch.zeros_like(self.E)
-        self.pm, self.pv = torch.zeros_like(self.P), torch.zeros_like(self.P)
-        self.vmax = torch.zeros_like(self.E) if amsgrad else None
-        self.pvmax = torch.zeros_like(self.P) if amsgrad else None
-        self._row_slot = torch.full((self.E.shape[0],), -1, dtype=torch.int32, device=device)
-        self.step = 0
+        self.item_fused = self._want_fused and ops.sage_supported(K, Ti, self.L, self.n)
+        self.user_fused = self._want_fused and u2i and ops.sage_supported(K, self.users.T, 0, 1)
 
     # ---- sampling -----------------------------------------------------------------------------
     def tree_ids(self, targets: torch.Tensor, step: int) -> torch.Tensor:
@@ -189,6 +194,10 @@ class SageNet:
         rows, scale = self.items.slots(self.tree_ids(targets, step))
         return _Tower(self, rows, scale, self.item_pack, self.L, self.n, step, train, self.item_fused)
 
+    def i2i_tower(self, queries, items_pos, items_neg, step):
+        """The three item towers of an i2i step as one batch."""
+        return self.item_tower(torch.cat([queries, items_pos, items_neg]).contiguous(), step, True)
+
     def user_tower(self, users, step, train):
         rows, scale = self.users.slots(users)
         return _Tower(self, rows, scale, self.user_pack, 0, 1, step, train, self.user_fused)
@@ -231,7 +240,7 @@ class SageNet:
             loss = self._loss(loss_type, q, r[:npos], r[npos:])
         else:
             qt = None
-            it = self.item_tower(torch.cat([queries, items_pos, items_neg]).contiguous(), step, True)
+            it = self.i2i_tower(queries, items_pos, items_neg, step)
             r = it.repr.clone().requires_grad_(True)
             loss = self._loss(loss_type, r[:nq], r[nq:nq + npos], r[nq + npos:])
         loss.backward()

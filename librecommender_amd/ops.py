@@ -2708,3 +2708,121 @@ def sage_bwd(table: torch.Tensor, rows: torch.Tensor, scale: Optional[torch.Tens
     _call("lr_sage_bwd_f32", _ptr(table), V, _ptr(rows), _ptr(scale), B, K, T, L, n, _ptr(params), float(dropout),
           int(seed) & _U64, int(step), _ptr(grepr), _ptr(grow), _ptr(gparams), _ptr(relu), _ptr(ws), ws.numel(), _stream())
     return grow, gparams, relu
+
+
+# --------------------------------------------------------------------------------------
+# PinSage: importance-walk sampling and the fused tower (csrc/pinsage.hip)
+# --------------------------------------------------------------------------------------
+def pinsage_supported(K: int, T: int, num_layers: int, num_neighbors: int) -> bool:
+    """`lr_pinsage_supported`: whether the fused tower takes this shape."""
+    return bool(_lib.load().lr_pinsage_supported(int(K), int(T), int(num_layers), int(num_neighbors)))
+
+
+def pinsage_param_floats(K: int, T: int, num_layers: int) -> int:
+    """Length of the parameter pack: proj W^T [T K, K], proj b [K]; per layer Q^T [K, K], bq [K], W^T [2 K, K], bw [K]; the
+    head G1^T [K, K], b1 [K], G2^T [K, K] (0: unsupported)."""
+    return _lib.load().lr_pinsage_params_bytes(int(K), int(T), int(num_layers)) // 4
+
+
+def pinsage_bwd_slabs(B: int, K: int, T: int, num_layers: int, num_neighbors: int) -> int:
+    return int(_lib.load().lr_pinsage_bwd_slabs(int(B), int(K), int(T), int(num_layers), int(num_neighbors)))
+
+
+def pinsage_neighbors(nodes: torch.Tensor, graph: SageGraph, num_neighbors: int, num_walks: int, walk_len: int,
+                      termination_prob: float, seed: int, step: int, level: int, tree_target: Optional[torch.Tensor] = None,
+                      tree_exclude: Optional[torch.Tensor] = None):
+    """`lr_pinsage_neighbors_i32` -> (ids, counts) int32 [n_nodes, num_neighbors]: the most visited items of the node's walks in
+    selection order, unused slots -1 / 0.  `tree_target` / `tree_exclude` int32 [n_trees] carry the i2i exclusion."""
+    _req(nodes, torch.int32, "nodes", 1)
+    nn, nw, wl = int(num_neighbors), int(num_walks), int(walk_len)
+    if not 1 <= nn <= 10:
+        raise ValueError("`num_neighbors` must be from 1 to 10")
+    if nw < 1 or wl < 1 or nw * wl > 64:
+        raise ValueError("`num_walks` and `neighbor_walk_len` must be at least 1 and their product at most 64")
+    if not float(termination_prob) == float(termination_prob):
+        raise ValueError("`termination_prob` must be a number")
+    n, n_trees = nodes.numel(), 0
+    if tree_exclude is not None:
+        _req(tree_exclude, torch.int32, "tree_exclude", 1)
+        if tree_target is None or _req(tree_target, torch.int32, "tree_target", 1).numel() != tree_exclude.numel():
+            raise ValueError("tree_target and tree_exclude must have the same length")
+        n_trees = tree_exclude.numel()
+        if n != n_trees * nn ** int(level):
+            raise ValueError("nodes must hold one level of every tree")
+    else:
+        tree_target = None
+    ids, counts = (torch.empty((max(n, 1), nn), dtype=torch.int32, device=nodes.device)[:n] for _ in range(2))
+    _call("lr_pinsage_neighbors_i32", _ptr(nodes), n, nn, nw, wl, float(termination_prob), _ptr(tree_target), _ptr(tree_exclude),
+          n_trees, *graph.args(), int(seed) & _U64, int(step), int(level), _ptr(ids), _ptr(counts), _stream())
+    return ids, counts
+
+
+def pinsage_weights(counts: torch.Tensor) -> torch.Tensor:
+    """The importance weights f32 of visit counts [n_nodes, num_neighbors]: count / row total, exactly 0 in an unused slot."""
+    c = counts.to(torch.float32)
+    return (c / c.sum(dim=1, keepdim=True).clamp(min=1.0)).contiguous()
+
+
+def _pinsage_check(table, rows, scale, weights, params, num_layers, num_neighbors, dropout):
+    _req(table, torch.float32, "table", 2)
+    _req(rows, torch.int32, "rows", 2)
+    _req(params, torch.float32, "params", 1)
+    V, K = table.shape
+    T = rows.shape[1]
+    N = sage_tree_nodes(num_layers, num_neighbors)
+    if not pinsage_supported(K, T, num_layers, num_neighbors):
+        raise ValueError(f"unsupported PinSage shape: K={K} T={T} num_layers={num_layers} num_neighbors={num_neighbors} "
+                         "(see `pinsage_supported`)")
+    if rows.shape[0] % N:
+        raise ValueError(f"rows must hold a whole number of trees of {N} nodes")
+    B = rows.shape[0] // N
+    if scale is not None and _req(scale, torch.float32, "scale", 2).shape != rows.shape:
+        raise ValueError("scale must have the shape of rows")
+    if N > 1 and (weights is None or _req(weights, torch.float32, "weights", 1).numel() != B * (N - 1)):
+        raise ValueError("weights must hold one value per node of the levels 1 .. num_layers")
+    if params.numel() != pinsage_param_floats(K, T, num_layers):
+        raise ValueError("params must be the parameter pack of this shape (see `pinsage_param_floats`)")
+    if not 0.0 <= float(dropout) < 1.0:
+        raise ValueError("`dropout_rate` must be in [0, 1)")
+    return B, K, T, V
+
+
+def pinsage_fwd(table: torch.Tensor, rows: torch.Tensor, scale: Optional[torch.Tensor], weights: Optional[torch.Tensor],
+                params: torch.Tensor, num_layers: int, num_neighbors: int, dropout: float = 0.0, seed: int = 0, step: int = 0,
+                train: bool = False) -> torch.Tensor:
+    """`lr_pinsage_fwd_f32`: repr [B, K] of B trees laid out as for `sage_fwd`, `weights` f32 [B (N - 1)] aligned with the nodes
+    of the levels 1 .. num_layers.  `train=False` is the inference mode: no dropout is drawn."""
+    B, K, T, V = _pinsage_check(table, rows, scale, weights, params, num_layers, num_neighbors, dropout)
+    repr_ = torch.empty((max(B, 1), K), dtype=torch.float32, device=table.device)[:B]
+    _call("lr_pinsage_fwd_f32", _ptr(table), V, _ptr(rows), _ptr(scale), _ptr(weights), B, K, T, int(num_layers),
+          int(num_neighbors), _ptr(params), float(dropout), int(seed) & _U64, int(step), 1 if train else 0, _ptr(repr_), _stream())
+    return repr_
+
+
+def pinsage_relu_rows(num_layers: int, num_neighbors: int) -> int:
+    """Rows of `relu_out` per tree: per layer the q flags and the w flags, then the head's row."""
+    L, n = int(num_layers), int(num_neighbors)
+    return sum(sage_tree_nodes(L - l, n) - 1 + sage_tree_nodes(L - l - 1, n) for l in range(L)) + 1
+
+
+def pinsage_bwd(table: torch.Tensor, rows: torch.Tensor, scale: Optional[torch.Tensor], weights: Optional[torch.Tensor],
+                params: torch.Tensor, num_layers: int, num_neighbors: int, grepr: torch.Tensor, dropout: float = 0.0,
+                seed: int = 0, step: int = 0, want_relu: bool = False):
+    """`lr_pinsage_bwd_f32` -> (grow [B N, T, K], gparams in the layout of `params`, relu flags uint8 or None)."""
+    B, K, T, V = _pinsage_check(table, rows, scale, weights, params, num_layers, num_neighbors, dropout)
+    _req(grepr, torch.float32, "grepr", 2)
+    if grepr.shape != (B, K):
+        raise ValueError("grepr must be [B, K]")
+    dev = table.device
+    n, L = int(num_neighbors), int(num_layers)
+    grow = torch.empty((max(rows.shape[0], 1), T, K), dtype=torch.float32, device=dev)[:rows.shape[0]]
+    gparams = torch.empty(params.numel(), dtype=torch.float32, device=dev)
+    relu = None
+    if want_relu:
+        n_relu = B * pinsage_relu_rows(L, n)
+        relu = torch.empty((max(n_relu, 1), K), dtype=torch.uint8, device=dev)[:n_relu]
+    ws = torch.empty(max(_lib.load().lr_pinsage_bwd_ws_bytes(B, K, T, L, n), 256), dtype=torch.uint8, device=dev)
+    _call("lr_pinsage_bwd_f32", _ptr(table), V, _ptr(rows), _ptr(scale), _ptr(weights), B, K, T, L, n, _ptr(params),
+          float(dropout), int(seed) & _U64, int(step), _ptr(grepr), _ptr(grow), _ptr(gparams), _ptr(relu), _ptr(ws), ws.numel(),
+          _stream())
+    return grow, gparams, relu
