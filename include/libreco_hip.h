@@ -622,7 +622,14 @@ int lr_owner_partition_i32(const int32_t* rows, const int32_t* n_seg, int64_t n_
  * The `_dense_` forms take already materialised q[B,K'] / keys[B,L,K'] (items with side
  * features: K' = K*(1+n_item_feats), tfops/features.py:204-218) instead of table + ids.
  * ---------------------------------------------------------------------------------- */
-size_t lr_din_attn_ws_bytes(int64_t B, int L, int K, int H);
+size_t lr_din_attn_ws_bytes(int64_t B, int L, int K, int H);   /* 0 where the backward has no kernel (lr_din_attn_path) */
+/* The supported (K, L) region, the one the dispatchers themselves use: 0 = no kernel (the entry points return LR_ESHAPE),
+ * 1 = the shuffle kernels, 2 = the MFMA kernels (the only ones that take `hid` / `order`).  K in {16, 32, 64, 128}; L <= 2048
+ * runs on the MFMA kernels; longer sequences run on the shuffle kernels while their LDS fits a workgroup's 160 KB:
+ *   forward   (64 K + 4 L) * 4 bytes:        L <= 9,984 / 9,728 / 9,216 / 8,192   at K = 16 / 32 / 64 / 128
+ *   backward  (256 K + 144 + 4 L) * 4 bytes: L <= 9,180 / 8,156 / 6,108 / none    at K = 16 / 32 / 64 / 128
+ * `backward` != 0 asks for the backward's region, which is the smaller one: a shape may have a forward and no backward. */
+int lr_din_attn_path(int K, int L, int backward);
 /* The id stream of the fused DIN step (nets/din_fused.py) in one launch: ids[(2 + n_plain + 2 + L) * B], plane-major
  * [users + user_off | items + item_off | sparse[b][cols[p]] + sparse_off (cols NULL: column p) | -1 (the attention-output plane) |
  *  items + item_off (the query rows) | seqs[b][l] + item_off for l < lens[b], else -1] — the global row ids of

@@ -210,7 +210,7 @@ __global__ __launch_bounds__(kBlock) void din_fwd_kernel(
       float sl = 0.f;
 #pragma unroll
       for (int i = 0; i < NV; ++i) sl = fmaf(w2v[i], sigmoidf_(A[i] + p[i]), sl);
-      const float s = (group_sum_rs<LPR>(sl) + b2v) * rsK;
+      const float s = din_mul_rounded(group_sum_rs<LPR>(sl) + b2v, rsK);  // rounded: not contracted into `s - mn` (see din_mfma.hpp)
       if (act) {
         const float mn = fmaxf(m, s);
         const float f = __expf(m - mn);  // m = -inf first time -> 0
@@ -491,6 +491,17 @@ static int set_lds(Kern kern, size_t lds) {
 static inline bool din_use_mfma(int K, int L) {
   return (K == 16 || K == 32 || K == 64 || K == 128) && L <= 2048;
 }
+// THE statement of the supported (K, L) region (lr_din_attn_path): 0 = no kernel, 1 = the shuffle kernels, 2 = the MFMA kernels.
+// Longer sequences than the MFMA kernels take run the shuffle kernels as far as their LDS fits a workgroup's 160 KB: the
+// forward keeps 4 K x 16 weights + [4 waves][L] scores, the backward 16 K x 16 floats of weights and per-wave accumulators on
+// top of its [4 waves][L] — so the backward's bound is the lower one, and K = 128 has no backward beyond L = 2048 at all
+// (131,648 B + 16 L <= 163,840 B gives L <= 2,012).
+constexpr size_t kDinMaxLds = 160 * 1024;
+static inline int din_path(int K, int L, bool backward) {
+  if (!(K == 16 || K == 32 || K == 64 || K == 128) || L < 1) return 0;
+  if (din_use_mfma(K, L)) return 2;
+  return (backward ? din_bwd_lds(K, L) : din_fwd_lds(K, L)) <= kDinMaxLds ? 1 : 0;
+}
 static inline size_t din_mfma_fwd_lds(int K, int L) { return size_t(3) * (K / 16) * 64 * 16 + size_t(4) * L * 4; }
 static inline size_t din_mfma_data_lds(int K, int L) {      // weight images, [4 waves][L] scores, [4 waves][2][K / 16][4] row pieces
   return size_t(6) * (K / 16) * 64 * 16 + size_t(4) * ((L + 3) & ~3) * 4 + size_t(4) * 2 * (K / 16) * 4 * 16;
@@ -512,8 +523,10 @@ static int din_fwd_dispatch(const float* qsrc, const float* ksrc, int64_t V, int
                             const float* b2, float* out, float* attn, hipStream_t s, float* hid = nullptr,
                             int32_t* order_out = nullptr) {
   const int grid = din_grid(B);
-  if ((hid != nullptr || order_out != nullptr) && !din_use_mfma(K, L)) return LR_ESHAPE;      // MFMA kernels only
-  if (din_use_mfma(K, L)) {
+  const int path = din_path(K, L, false);
+  if (path == 0) return LR_ESHAPE;
+  if ((hid != nullptr || order_out != nullptr) && path != 2) return LR_ESHAPE;      // MFMA kernels only
+  if (path == 2) {
     const size_t lds_m = din_mfma_fwd_lds(K, L);
 #define LR_DINFM(NT)                                                                          \
   {                                                                                           \
@@ -531,7 +544,6 @@ static int din_fwd_dispatch(const float* qsrc, const float* ksrc, int64_t V, int
 #undef LR_DINFM
   }
   const size_t lds = din_fwd_lds(K, L);
-  if (lds > 160 * 1024) return LR_ESHAPE;
 #define LR_DINF(LPR)                                                                         \
   {                                                                                          \
     auto kern = din_fwd_kernel<LPR, GATHER>;                                                 \
@@ -558,8 +570,10 @@ static int din_bwd_dispatch(const float* qsrc, const float* ksrc, int64_t V, int
                             size_t ws_bytes, hipStream_t s, int parts = 3, int keep_pad_rows = 0,
                             const float* hid = nullptr, const int32_t* order = nullptr) {
   const int grid = din_grid(B);
-  if ((hid != nullptr || order != nullptr) && !din_use_mfma(K, L)) return LR_ESHAPE;
-  if (din_use_mfma(K, L)) {
+  const int path = din_path(K, L, true);
+  if (path == 0) return LR_ESHAPE;
+  if ((hid != nullptr || order != nullptr) && path != 2) return LR_ESHAPE;
+  if (path == 2) {
     if (ws == nullptr || ws_bytes < din_mfma_ws_floats(B, L, K) * 4) return LR_EWORKSPACE;
     float* dzbuf = static_cast<float*>(ws);
     float* Dzbuf = dzbuf + static_cast<size_t>(B) * L * kDH;
@@ -605,7 +619,6 @@ static int din_bwd_dispatch(const float* qsrc, const float* ksrc, int64_t V, int
   }
   if (!(parts & 1)) return LR_OK;     // the shuffle kernel computes everything in the data part
   const size_t lds = din_bwd_lds(K, L);
-  if (lds > 160 * 1024) return LR_ESHAPE;
   const size_t need = static_cast<size_t>(grid) * din_partial_floats(K) * 4;
   if (ws == nullptr || ws_bytes < need) return LR_EWORKSPACE;
   float* partial = static_cast<float*>(ws);
@@ -622,8 +635,7 @@ static int din_bwd_dispatch(const float* qsrc, const float* ksrc, int64_t V, int
     case 16: LR_DINB(4)
     case 32: LR_DINB(8)
     case 64: LR_DINB(16)
-    case 128: LR_DINB(32)
-    default: return LR_ESHAPE;
+    default: return LR_ESHAPE;     // (K = 128: din_path has no shuffle backward, its LDS exceeds a workgroup's at every L > 2048)
   }
 #undef LR_DINB
   int rc = launch_status();
@@ -639,10 +651,14 @@ using namespace lr;
 
 extern "C" size_t lr_din_attn_ws_bytes(int64_t B, int L, int K, int H) {
   if (B < 0 || H != kH || K < 1 || L < 1) return 0;
+  const int path = din_path(K, L, true);
+  if (path == 0) return 0;                       // no backward for this shape: nothing to size
   const size_t shuffle = static_cast<size_t>(din_grid(B)) * din_partial_floats(K) * 4;
-  const size_t mfma = din_use_mfma(K, L) ? din_mfma_ws_floats(B, L, K) * 4 : 0;
+  const size_t mfma = path == 2 ? din_mfma_ws_floats(B, L, K) * 4 : 0;
   return shuffle > mfma ? shuffle : mfma;
 }
+
+extern "C" int lr_din_attn_path(int K, int L, int backward) { return din_path(K, L, backward != 0); }
 
 #define LR_DIN_COMMON_CHECK()                                                          \
   LR_CHECK_ARG(B >= 0 && L >= 1 && K >= 1);                                            \

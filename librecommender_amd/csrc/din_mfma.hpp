@@ -30,6 +30,12 @@ __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 __device__ __forceinline__ float din_sigmoid(float z) { return __frcp_rn(1.f + __expf(-z)); }
+// a product that is rounded to f32 and never contracted into a following add or subtract (HIP's __fmul_rn is a plain
+// operator in a header compiled with contraction on: it would still fuse)
+__device__ __forceinline__ float din_mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
 
 // sum over the 16 lanes of a DPP row (lanes with equal lane / 16); every lane gets the total
 __device__ __forceinline__ float row_sum16(float x) {
@@ -364,7 +370,11 @@ __global__ __launch_bounds__(kBlock, 2) void din_fwd_mfma_kernel(
         hh[r] = din_sigmoid((a0[r] + a1[r]) + zq[r]);
         s = fmaf(w2r[r], hh[r], s);
       }
-      s = (group_sum4(s) + b2v) * rsK;
+      // (the score is ROUNDED here.  Left contractible, `s - mn` below became fma(x, rsK, -mn) on the unrounded
+      // product, so the key that sets the maximum entered `den` as exp(its rounding residue) instead of 1, while `attn` is
+      // formed from the rounded scores in `sc`: the weights of a row then missed 1 by up to half an ulp of the score —
+      // 8e-6 at scores near 190 — and the backward's sum of a_l (da_l - dot) no longer cancelled.)
+      s = din_mul_rounded(group_sum4(s) + b2v, rsK);
       if (act && hid != nullptr) st4(hid + (b * L + l) * kDH + 4 * kq, make_float4(hh[0], hh[1], hh[2], hh[3]));
       if (act) {
         const float mn = fmaxf(m, s);

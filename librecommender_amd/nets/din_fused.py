@@ -247,6 +247,8 @@ class FusedDINStep:
         Pn = Fp + 1
         f32 = dict(dtype=torch.float32, device=dev)
         i32 = dict(dtype=torch.int32, device=dev)
+        if ops.din_path(K, L, backward=True) == 0:   # (a forward-only shape would predict, then fail at its first backward)
+            raise ValueError(f"the fused DIN step has no attention backward kernel for K = {K}, L = {L} (ops.din_path)")
         b = _Bufs()
         b.B, b.L, b.Fp, b.Pn = B, L, Fp, Pn
         b.xbuf = torch.empty((Pn, B, K), **f32)
@@ -262,7 +264,7 @@ class FusedDINStep:
         lib = ops._lib.load()
         b.att_ws = torch.empty(max(lib.lr_din_attn_ws_bytes(B, L, K, 16), 8), dtype=torch.uint8, device=dev)
         # the attention MLP's hidden activations, forward -> backward (26 MB at cfg 3): the backward does not recompute them
-        mfma_shape = K in (16, 32, 64, 128) and L <= 2048
+        mfma_shape = ops.din_path(K, L) == 2
         # the samples in the order the backward attention kernels' waves take them (written by the forward's launch: balanced by length)
         b.order = torch.empty(B, **i32) if mfma_shape and os.environ.get("LIBRECO_DIN_ORDER", "1") != "0" else None
         b.att_hid = (torch.empty(ops.din_hid_floats(B, L, K, b.order is not None), **f32)

@@ -1227,6 +1227,23 @@ def _din_params(W1, b1, W2, b2, K):
     return H
 
 
+def din_path(K: int, L: int, backward: bool = False) -> int:
+    """The kernels a DIN attention shape runs on (`lr_din_attn_path`, the dispatchers' own statement of the region):
+    0 = none, 1 = the shuffle kernels (L > 2048 while their LDS fits), 2 = the MFMA kernels (the only ones that take
+    `hid` / `order`).  The backward's region is the smaller one."""
+    return int(_lib.load().lr_din_attn_path(int(K), int(L), int(bool(backward))))
+
+
+def _din_require(K, L, backward, what, mfma_only=False):
+    path = din_path(K, L, backward)
+    side = "backward" if backward else "forward"
+    if path == 0:
+        raise ValueError(f"{what}: no DIN attention {side} kernel for K = {K}, L = {L} (ops.din_path)")
+    if mfma_only and path != 2:
+        raise ValueError(f"{what}: `hid` / `order` need the MFMA kernels, K = {K}, L = {L} runs the shuffle {side} (ops.din_path)")
+    return path
+
+
 def din_attn_pool_fwd(item_table: torch.Tensor, item: torch.Tensor, seq: torch.Tensor,
                       seq_len: torch.Tensor, W1, b1, W2, b2, out=None, attn=None, hid=None, order_out=None):
     """Fused gather + din_attention (algorithms/din.py:241-250, layers/attention.py:28-64).  `out` [B, K] / `attn`
@@ -1240,6 +1257,7 @@ def din_attn_pool_fwd(item_table: torch.Tensor, item: torch.Tensor, seq: torch.T
     V, K = item_table.shape
     B, L = seq.shape
     H = _din_params(W1, b1, W2, b2, K)
+    _din_require(K, L, False, "din_attn_pool_fwd", hid is not None or order_out is not None)
     if out is None:
         out = torch.empty((B, K), dtype=torch.float32, device=item_table.device)
     if attn is None:
@@ -1281,6 +1299,7 @@ def din_attn_pool_bwd(item_table, item, seq, seq_len, W1, b1, W2, b2, attn, gout
     V, K = item_table.shape
     B, L = seq.shape
     H = _din_params(W1, b1, W2, b2, K)
+    _din_require(K, L, True, "din_attn_pool_bwd", hid is not None or order is not None)
     dev = item_table.device
     lib = _lib.load()
     need = max(lib.lr_din_attn_ws_bytes(B, L, K, H), 8)
@@ -1314,6 +1333,7 @@ def din_attn_dense_fwd(q, keys, seq_len, W1, b1, W2, b2):
     _req(seq_len, torch.int32, "seq_len", 1)
     B, L, K = keys.shape
     H = _din_params(W1, b1, W2, b2, K)
+    _din_require(K, L, False, "din_attn_dense_fwd")
     out = torch.empty((B, K), dtype=torch.float32, device=q.device)
     attn = torch.empty((B, L), dtype=torch.float32, device=q.device)
     _call("lr_din_attn_dense_fwd_f32", _ptr(q), _ptr(keys), K, _ptr(seq_len), B, L,
@@ -1327,6 +1347,7 @@ def din_attn_dense_bwd(q, keys, seq_len, W1, b1, W2, b2, attn, gout):
     _req(keys, torch.float32, "keys", 3)
     B, L, K = keys.shape
     H = _din_params(W1, b1, W2, b2, K)
+    _din_require(K, L, True, "din_attn_dense_bwd")
     dev = q.device
     lib = _lib.load()
     ws = torch.empty(max(lib.lr_din_attn_ws_bytes(B, L, K, H), 8), dtype=torch.uint8, device=dev)
