@@ -1375,6 +1375,27 @@ int lr_pinsage_bwd_f32(const float* table, int64_t V, const int32_t* rows, const
                        int64_t step, const float* grepr, float* grow, float* gparams, uint8_t* relu_out, void* ws,
                        size_t ws_bytes, lr_stream_t stream);
 
+/* ---- FTRL-proximal (the wide side of Wide & Deep; csrc/ftrl.hip) -------------------------------------------------------
+ * TF1's ApplyFtrl / SparseApplyFtrl with lr_power = -0.5 and no l2 shrinkage, per element with gradient g:
+ *   new_accum = accum + g*g;  linear += g - (sqrt(new_accum) - sqrt(accum)) / lr * var;
+ *   var = |linear| > l1 ? (sign(linear)*l1 - linear) / (sqrt(new_accum)/lr + 2*l2) : 0;  accum = new_accum.
+ * lr > 0, l1 >= 0, l2 >= 0.  TF's slots start at accum = 0.1, linear = 0.
+ *
+ * lr_ftrl_rows_f32: `var`, `accum`, `linear` are scalar-row tables of V floats; `grad` holds one float per position of the
+ *   segments (lr_segments_build; n positions, n_seg read on the device).  The gradient of a distinct row is the sum over its
+ *   run, added in a fixed order that does not depend on the grid (no float atomics: two calls give the same bits); the row's
+ *   three values are read and written once, rows outside the stream are not written.  Runs of more than 32 positions are cut
+ *   into 256-position chunks summed by one wave each when a workspace of lr_ftrl_rows_ws_bytes(n) bytes is passed (`ws`;
+ *   NULL: every run is walked by one lane; contents arbitrary on entry).  A non-NULL `ws` with ws_bytes below that size:
+ *   LR_EWORKSPACE.  n == 0: nothing is launched.
+ * lr_ftrl_dense_f32: the same update on every element of a flat range of n floats with g = grad[i] + l2_grad_coef * var[i]. */
+size_t lr_ftrl_rows_ws_bytes(int64_t n_max);
+int lr_ftrl_rows_f32(float* var, float* accum, float* linear, int64_t V, const float* grad, const int32_t* seg_pos,
+                     const int32_t* seg_rows, const int32_t* seg_start, const int32_t* n_seg, int64_t n, double lr, double l1,
+                     double l2, void* ws, size_t ws_bytes, lr_stream_t stream);
+int lr_ftrl_dense_f32(float* var, float* accum, float* linear, int64_t n, const float* grad, double l2_grad_coef, double lr,
+                      double l1, double l2, lr_stream_t stream);
+
 /* Measurement probe (scripts/mfma_peak.py): iters x 8 back-to-back v_mfma_f32_32x32x2_f32 per wave on
  * 256 x waves_per_simd workgroups — the f32 MFMA rate the chip sustains at the clock it holds under that load. */
 int lr_mfma_f32_probe(int iters, int waves_per_simd, float* out, lr_stream_t stream);

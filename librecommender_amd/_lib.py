@@ -287,6 +287,9 @@ SIGNATURES = {
                                   _p]),
     "lr_pinsage_bwd_f32": (_int, [_p, _i64, _p, _p, _p, _i64, _int, _int, _int, _int, _p, C.c_double, C.c_uint64, _i64, _p, _p, _p,
                                   _p, _p, _sz, _p]),
+    "lr_ftrl_rows_ws_bytes": (_sz, [_i64]),
+    "lr_ftrl_rows_f32": (_int, [_p, _p, _p, _i64, _p, _p, _p, _p, _p, _i64, C.c_double, C.c_double, C.c_double, _p, _sz, _p]),
+    "lr_ftrl_dense_f32": (_int, [_p, _p, _p, _i64, _p, C.c_double, C.c_double, C.c_double, C.c_double, _p]),
 }
 
 _lib = None

@@ -20,7 +20,8 @@ from .transformer import Transformer
 from .two_tower import TwoTower
 from .user_cf import UserCF
 from .wavenet import WaveNet
+from .wide_deep import WideDeep
 from .youtube_ranking import YouTubeRanking
 from .youtube_retrieval import YouTubeRetrieval
 
-__all__ = ["ALS", "AutoInt", "BPR", "Caser", "DIN", "DeepFM", "DeepWalk", "FM", "GraphSage", "Item2Vec", "ItemCF", "LightGCN", "NGCF", "PinSage", "RNN4Rec", "SIM", "SVD", "SVDpp", "Swing", "Transformer", "TwoTower", "UserCF", "WaveNet", "YouTubeRanking", "YouTubeRetrieval"]
+__all__ = ["ALS", "AutoInt", "BPR", "Caser", "DIN", "DeepFM", "DeepWalk", "FM", "GraphSage", "Item2Vec", "ItemCF", "LightGCN", "NGCF", "PinSage", "RNN4Rec", "SIM", "SVD", "SVDpp", "Swing", "Transformer", "TwoTower", "UserCF", "WaveNet", "WideDeep", "YouTubeRanking", "YouTubeRetrieval"]

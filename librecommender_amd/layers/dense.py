@@ -94,8 +94,22 @@ class DenseParams:
             self.v.copy_(torch.from_numpy(arrays["opt::dense_v"]))
         return all_match
 
-    def adam_step(self, hp) -> None:
-        """`hp`: by-value hyper-parameters or an `ops.AdamCoefBuffer` (graph-captured steps)."""
+    def span(self, first: str, last: str):
+        """(start, stop) of the flat buffer from the first element of parameter `first` to the padded end of `last`."""
+        start = self.params[first].storage_offset()
+        n = self.params[last].numel()
+        return start, self.params[last].storage_offset() + -(-n // 4) * 4
+
+    def adam_step(self, hp, skip=None) -> None:
+        """`hp`: by-value hyper-parameters or an `ops.AdamCoefBuffer` (graph-captured steps).  `skip` = (start, stop): a range of
+        the flat buffer that another optimiser owns (Wide & Deep: FTRL on the wide parameters); Adam moves what lies around it."""
+        if skip is not None:
+            with torch.no_grad():
+                for a, b in ((0, skip[0]), (skip[1], self.flat.numel())):
+                    if b > a:
+                        ops.adam_dense(self.flat[a:b].view(-1, 1), self.m[a:b].view(-1, 1), self.v[a:b].view(-1, 1), hp,
+                                       grows=self.grad[a:b])
+            return
         with torch.no_grad():
             if isinstance(hp, ops.AdamCoefBuffer):
                 ops.adam_dense_dc(self.flat, self.m, self.v, self.grad, hp)

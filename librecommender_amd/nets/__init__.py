@@ -11,7 +11,8 @@ from .rnn_nets import RNN4RecNet
 from .sage_net import SageNet
 from .pinsage_net import PinSageNet
 from .wavenet_net import WaveNetNet
+from .wide_deep_net import WideDeepNet
 from .tower_nets import ShardedTwoTowerNet, TwoTowerNet
 
 __all__ = ["DeepFMNet", "FMNet", "ShardedDeepFMNet", "ShardedFMNet", "FieldParallelDeepFMNet", "TwoTowerNet", "ShardedTwoTowerNet", "FeatEmbedding",
-           "FeatSpec", "FeatDeepFMNet", "FeatDINNet", "FeatFMNet", "FeatYouTubeRankingNet", "ShardedDINNet", "NGCFNet", "RNN4RecNet", "WaveNetNet", "FeatAutoIntNet", "CaserNet", "SageNet", "PinSageNet"]
+           "FeatSpec", "FeatDeepFMNet", "FeatDINNet", "FeatFMNet", "FeatYouTubeRankingNet", "ShardedDINNet", "NGCFNet", "RNN4RecNet", "WaveNetNet", "FeatAutoIntNet", "CaserNet", "SageNet", "PinSageNet", "WideDeepNet"]

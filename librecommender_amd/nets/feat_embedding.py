@@ -174,7 +174,9 @@ class FeatEmbedding:
         """Rows the plain streams of `_streams` occupy in front of an extra stream."""
         return int(ctx.idx_plain.numel() + sum(fi.numel() for fi in ctx.pooled_idx))
 
-    def apply_gradients(self, ctx: FeatCtx, hp, dense_adam=False, l2=0.0, extra=None, grads=None):
+    def apply_gradients(self, ctx: FeatCtx, hp, dense_adam=False, l2=0.0, extra=None, grads=None, lin_update=None):
+        """`lin_update(seg, gl)`: the caller's own optimiser for the `lin` table on the segments built here (Wide & Deep: FTRL);
+        Adam then leaves `lin` and its slots alone."""
         t = self.tables
         ids, g, gl = self._streams(ctx, extra, grads)
         seg = ops.build_segments(ids, t.V)
@@ -183,7 +185,9 @@ class FeatEmbedding:
             self._adam = RowAdam(self.device, *form)
         # two launches of the plain kernel, not `lin=`: that one has no long-run path, and these streams have Zipf heads
         self._adam.update(hp, seg, t.embed, t.m, t.v, g)
-        if gl is not None:
+        if gl is not None and lin_update is not None:
+            lin_update(seg, gl)
+        elif gl is not None:
             self._adam.update(hp, seg, t.lin, t.lin_m, t.lin_v, gl)
 
     @torch.no_grad()

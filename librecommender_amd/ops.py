@@ -170,6 +170,10 @@ class Segments:
         """Persistent workspace for the long-run (Zipf head) path of the scatter kernels (see lr_embed_scatter_ws_bytes)."""
         return self.owner.long_ws(K) if self.owner is not None and hasattr(self.owner, "long_ws") else None
 
+    def ftrl_ws(self) -> Optional[torch.Tensor]:
+        """Persistent workspace for the long-run path of `ftrl_rows` (see lr_ftrl_rows_ws_bytes)."""
+        return self.owner.ftrl_ws() if self.owner is not None and hasattr(self.owner, "ftrl_ws") else None
+
     def count(self) -> int:
         """Host sync — for tests and logging only."""
         return int(self.n_seg.item())
@@ -202,6 +206,14 @@ class SegmentBuilder:
         if ws is None:
             ws = self._long_ws[("hist", K)] = torch.empty(max(_lib.load().lr_svdpp_hist_grad_ws_bytes(self.n_max, K), 256),
                                                           dtype=torch.uint8, device=self.device)
+        return ws
+
+    def ftrl_ws(self) -> torch.Tensor:
+        """Persistent workspace of `lr_ftrl_rows_f32` for up to `n_max` positions (contents arbitrary between calls)."""
+        ws = self._long_ws.get("ftrl")
+        if ws is None:
+            ws = self._long_ws["ftrl"] = torch.empty(max(_lib.load().lr_ftrl_rows_ws_bytes(self.n_max), 256),
+                                                     dtype=torch.uint8, device=self.device)
         return ws
 
     def build(self, idx: torch.Tensor, want_slots: bool = False) -> Segments:
@@ -427,6 +439,60 @@ def adam_dense(table: torch.Tensor, m: torch.Tensor, v: torch.Tensor, hp: AdamHP
                                         _ptr(seg.rows) if n_max else 0,
                                         _ptr(seg.n_seg) if n_max else 0, n_max,
                                         _ptr(row_slot) if n_max else 0, float(l2), hp, _stream())
+
+
+# --------------------------------------------------------------------------------------
+# FTRL-proximal on scalar rows (csrc/ftrl.hip)
+# --------------------------------------------------------------------------------------
+FTRL_LONG_RUN = 32      # kFtrlLongRun / kFtrlChunk of csrc/ftrl.hip: a run of more positions than FTRL_LONG_RUN is cut into
+FTRL_CHUNK = 256        # chunks of FTRL_CHUNK positions (tests/test_wide_deep_cpu.py compares both with the source)
+FTRL_INIT_ACCUM = 0.1   # tf.train.FtrlOptimizer's initial_accumulator_value; the linear slot starts at 0
+_FTRL_WS_AUTO = object()
+
+
+def _ftrl_slots(var, accum, linear):
+    _req(var, torch.float32, "var")
+    _req(accum, torch.float32, "accum")
+    _req(linear, torch.float32, "linear")
+    if accum.numel() != var.numel() or linear.numel() != var.numel():
+        raise ValueError("shape mismatch: var, accum and linear must have the same number of elements")
+
+
+def _ftrl_hp(lr, l1, l2):
+    if not lr > 0 or l1 < 0 or l2 < 0:
+        raise ValueError(f"FTRL needs lr > 0, l1 >= 0 and l2 >= 0, got lr={lr}, l1={l1}, l2={l2}")
+    return float(lr), float(l1), float(l2)
+
+
+def ftrl_rows(var: torch.Tensor, accum: torch.Tensor, linear: torch.Tensor, grad: torch.Tensor, seg: Segments, lr: float,
+              l1: float = 1e-3, l2: float = 0.0, ws=_FTRL_WS_AUTO) -> None:
+    """Row-wise FTRL-proximal on a scalar-row table ([V] or [V, 1]) from the per-position gradients `grad` ([seg.n] or
+    [seg.n, 1]): each distinct row takes the sum over its run and is read and written once (`lr_ftrl_rows_f32`).
+    `ws`: the long-run workspace, by default the persistent one of the segments' builder; None walks every run with one lane."""
+    _ftrl_slots(var, accum, linear)
+    _req(grad, torch.float32, "grad")
+    if var.dim() > 2 or (var.dim() == 2 and var.shape[1] != 1):
+        raise ValueError(f"var must be a scalar-row table [V] or [V, 1], got shape {tuple(var.shape)}")
+    if grad.numel() != seg.n or var.numel() != seg.V:
+        raise ValueError("shape mismatch: one gradient per segmented position, one row per id of the segments")
+    hp = _ftrl_hp(lr, l1, l2)
+    if ws is _FTRL_WS_AUTO:
+        ws = seg.ftrl_ws()
+    if ws is not None:
+        _req(ws, torch.uint8, "ws", 1)
+    _call("lr_ftrl_rows_f32", _ptr(var), _ptr(accum), _ptr(linear), var.numel(), _ptr(grad), _ptr(seg.pos), _ptr(seg.rows),
+          _ptr(seg.start), _ptr(seg.n_seg), seg.n, *hp, _ptr(ws), 0 if ws is None else ws.numel(), _stream())
+
+
+def ftrl_dense(var: torch.Tensor, accum: torch.Tensor, linear: torch.Tensor, grad: torch.Tensor, lr: float, l1: float = 1e-3,
+               l2: float = 0.0, l2_grad_coef: float = 0.0) -> None:
+    """FTRL-proximal on every element of `var` with the gradient `grad + l2_grad_coef * var` (`lr_ftrl_dense_f32`)."""
+    _ftrl_slots(var, accum, linear)
+    _req(grad, torch.float32, "grad")
+    if grad.numel() != var.numel():
+        raise ValueError("shape mismatch: the dense gradient must have the parameter's size")
+    hp = _ftrl_hp(lr, l1, l2)
+    _call("lr_ftrl_dense_f32", _ptr(var), _ptr(accum), _ptr(linear), var.numel(), _ptr(grad), float(l2_grad_coef), *hp, _stream())
 
 
 # --------------------------------------------------------------------------------------
