@@ -1396,6 +1396,33 @@ int lr_ftrl_rows_f32(float* var, float* accum, float* linear, int64_t V, const f
 int lr_ftrl_dense_f32(float* var, float* accum, float* linear, int64_t n, const float* grad, double l2_grad_coef, double lr,
                       double l1, double l2, lr_stream_t stream);
 
+/* ---- NCF (csrc/ncf.hip): the two-field front and back of a step, and the inference tower in one launch -------------------
+ * u = table[user row], i = table[item row] (global rows of ONE [V, K] table; an id outside [0, V) reads as a zero row, as in
+ * lr_embed_gather_f32).  K % 4 == 0, 4 <= K <= 128; table, x, gmf, G, wg and every W[l] 16-byte aligned (LR_EINVAL otherwise).
+ *
+ * lr_ncf_pair_fwd_f32: idx [B, 2] = (user row, item row) per sample -> x [B, 2K] = [u | i] and gmf [B, K] = u * i, one f32
+ *   multiply per element (bit-exact against numpy f32).
+ * lr_ncf_pair_bwd_f32: adds the GMF path to the MLP's row gradient in place:
+ *   G[b, k] = fmaf(gl[b] * wg[k], x[b, K + k], G[b, k]),  G[b, K + k] = fmaf(gl[b] * wg[k], x[b, k], G[b, K + k]);
+ *   afterwards G viewed [2B, K] is the per-position gradient in the order of idx viewed [2B].
+ * lr_ncf_score_f32: out[p] = sum_k u_k i_k wg[k] + h_L . wd + c for the n pairs (users[p], items[p]), where x = [u | i],
+ *   h_l = relu(h_{l-1} W[l] + b[l]) * s[l] + t[l] for l < L and h_L = h_{L-1} W[L] + b[L] (W[l] row-major [d_in, widths[l]];
+ *   `W`, `b`, `s`, `t`: host arrays of n_layers device pointers; `s` / `t` or single entries of both may be NULL: identity;
+ *   the entries of the last layer are ignored).  The caller folds an input BatchNorm into (W[0], b[0]) and passes each hidden
+ *   BatchNorm's inference affine as (s, t).  One launch: workgroups of 256 threads take 64 pairs per pass and stay resident
+ *   over the tiles, the weights are staged into LDS once per workgroup, products run on v_mfma_f32_32x32x2_f32.  Every
+ *   output is one k-ordered f32 fma chain per product; no atomics: two calls give the same bits.
+ *   Envelope (lr_ncf_score_supported, the single source of truth): K as above, 1 <= n_layers <= 4, widths multiples of 16 in
+ *   [16, 256], and weights ([d_in][widths[l] rounded up to 32]) + two [width][68] activation tiles within 160 KB of LDS.
+ *   Outside it: LR_ESHAPE, nothing is written. */
+int lr_ncf_pair_fwd_f32(const float* table, int64_t V, int K, const int32_t* idx, int64_t B, float* x, float* gmf,
+                        lr_stream_t stream);
+int lr_ncf_pair_bwd_f32(const float* x, const float* gl, const float* wg, float* G, int64_t B, int K, lr_stream_t stream);
+int lr_ncf_score_supported(int K, int n_layers, const int* widths);
+int lr_ncf_score_f32(const float* table, int64_t V, int K, const int32_t* users, const int32_t* items, int64_t n, int n_layers,
+                     const int* widths, const float* const* W, const float* const* b, const float* const* s,
+                     const float* const* t, const float* wg, const float* wd, float c, float* out, lr_stream_t stream);
+
 /* Measurement probe (scripts/mfma_peak.py): iters x 8 back-to-back v_mfma_f32_32x32x2_f32 per wave on
  * 256 x waves_per_simd workgroups — the f32 MFMA rate the chip sustains at the clock it holds under that load. */
 int lr_mfma_f32_probe(int iters, int waves_per_simd, float* out, lr_stream_t stream);

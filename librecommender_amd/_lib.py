@@ -290,6 +290,10 @@ SIGNATURES = {
     "lr_ftrl_rows_ws_bytes": (_sz, [_i64]),
     "lr_ftrl_rows_f32": (_int, [_p, _p, _p, _i64, _p, _p, _p, _p, _p, _i64, C.c_double, C.c_double, C.c_double, _p, _sz, _p]),
     "lr_ftrl_dense_f32": (_int, [_p, _p, _p, _i64, _p, C.c_double, C.c_double, C.c_double, C.c_double, _p]),
+    "lr_ncf_pair_fwd_f32": (_int, [_p, _i64, _int, _p, _i64, _p, _p, _p]),
+    "lr_ncf_pair_bwd_f32": (_int, [_p, _p, _p, _p, _i64, _int, _p]),
+    "lr_ncf_score_supported": (_int, [_int, _int, _p]),
+    "lr_ncf_score_f32": (_int, [_p, _i64, _int, _p, _p, _i64, _int, _p, _p, _p, _p, _p, _p, _p, _f32, _p, _p]),
 }
 
 _lib = None

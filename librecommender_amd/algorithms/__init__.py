@@ -9,6 +9,7 @@ from .graphsage import GraphSage
 from .item2vec import Item2Vec
 from .item_cf import ItemCF
 from .lightgcn import LightGCN
+from .ncf import NCF
 from .ngcf import NGCF
 from .pinsage import PinSage
 from .rnn4rec import RNN4Rec
@@ -24,4 +25,4 @@ from .wide_deep import WideDeep
 from .youtube_ranking import YouTubeRanking
 from .youtube_retrieval import YouTubeRetrieval
 
-__all__ = ["ALS", "AutoInt", "BPR", "Caser", "DIN", "DeepFM", "DeepWalk", "FM", "GraphSage", "Item2Vec", "ItemCF", "LightGCN", "NGCF", "PinSage", "RNN4Rec", "SIM", "SVD", "SVDpp", "Swing", "Transformer", "TwoTower", "UserCF", "WaveNet", "WideDeep", "YouTubeRanking", "YouTubeRetrieval"]
+__all__ = ["ALS", "AutoInt", "BPR", "Caser", "DIN", "DeepFM", "DeepWalk", "FM", "GraphSage", "Item2Vec", "ItemCF", "LightGCN", "NCF", "NGCF", "PinSage", "RNN4Rec", "SIM", "SVD", "SVDpp", "Swing", "Transformer", "TwoTower", "UserCF", "WaveNet", "WideDeep", "YouTubeRanking", "YouTubeRetrieval"]

@@ -6,6 +6,7 @@ from .feat_embedding import FeatEmbedding, FeatSpec
 from .feat_nets import FeatDeepFMNet, FeatDINNet, FeatFMNet, FeatYouTubeRankingNet, ShardedDINNet
 from .field_parallel import FieldParallelDeepFMNet
 from .fm_nets import DeepFMNet, FMNet, ShardedDeepFMNet, ShardedFMNet
+from .ncf_net import NCFNet
 from .ngcf_net import NGCFNet
 from .rnn_nets import RNN4RecNet
 from .sage_net import SageNet
@@ -15,4 +16,4 @@ from .wide_deep_net import WideDeepNet
 from .tower_nets import ShardedTwoTowerNet, TwoTowerNet
 
 __all__ = ["DeepFMNet", "FMNet", "ShardedDeepFMNet", "ShardedFMNet", "FieldParallelDeepFMNet", "TwoTowerNet", "ShardedTwoTowerNet", "FeatEmbedding",
-           "FeatSpec", "FeatDeepFMNet", "FeatDINNet", "FeatFMNet", "FeatYouTubeRankingNet", "ShardedDINNet", "NGCFNet", "RNN4RecNet", "WaveNetNet", "FeatAutoIntNet", "CaserNet", "SageNet", "PinSageNet", "WideDeepNet"]
+           "FeatSpec", "FeatDeepFMNet", "FeatDINNet", "FeatFMNet", "FeatYouTubeRankingNet", "ShardedDINNet", "NGCFNet", "RNN4RecNet", "WaveNetNet", "FeatAutoIntNet", "CaserNet", "SageNet", "PinSageNet", "WideDeepNet", "NCFNet"]

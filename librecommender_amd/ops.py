@@ -496,6 +496,100 @@ def ftrl_dense(var: torch.Tensor, accum: torch.Tensor, linear: torch.Tensor, gra
 
 
 # --------------------------------------------------------------------------------------
+# NCF: the two-field front / back of a step and the one-launch inference tower (csrc/ncf.hip)
+# --------------------------------------------------------------------------------------
+def _ncf_k(K: int) -> int:
+    if K % 4 or not 4 <= K <= 128:
+        raise ValueError(f"the NCF kernels take K % 4 == 0, 4 <= K <= 128, got K={K}")
+    return int(K)
+
+
+def ncf_pair_fwd(table: torch.Tensor, idx: torch.Tensor, x: Optional[torch.Tensor] = None, gmf: Optional[torch.Tensor] = None):
+    """`idx` [B, 2] global (user row, item row) -> x [B, 2K] = [u | i] and gmf [B, K] = u * i, one f32 multiply per element; an
+    id outside the table reads as a zero row (`lr_ncf_pair_fwd_f32`).  `x` / `gmf`: buffers of at least B rows to write into."""
+    _req(table, torch.float32, "table", 2)
+    _req(idx, torch.int32, "idx", 2)
+    V, K = table.shape
+    _ncf_k(K)
+    B = idx.shape[0]
+    if idx.shape[1] != 2:
+        raise ValueError(f"shape mismatch: idx must be [B, 2], got {tuple(idx.shape)}")
+    x = torch.empty((B, 2 * K), dtype=torch.float32, device=table.device) if x is None else _req(x, torch.float32, "x", 2)
+    gmf = torch.empty((B, K), dtype=torch.float32, device=table.device) if gmf is None else _req(gmf, torch.float32, "gmf", 2)
+    if x.shape[0] < B or x.shape[1] != 2 * K or gmf.shape[0] < B or gmf.shape[1] != K:
+        raise ValueError("shape mismatch: x must be [>= B, 2K] and gmf [>= B, K]")
+    _call("lr_ncf_pair_fwd_f32", _ptr(table), V, K, _ptr(idx), B, _ptr(x), _ptr(gmf), _stream())
+    return x, gmf
+
+
+def ncf_pair_bwd_(x: torch.Tensor, gl: torch.Tensor, wg: torch.Tensor, G: torch.Tensor, B: Optional[int] = None) -> torch.Tensor:
+    """In place on the MLP's row gradient `G` [B, 2K]: G[b, :K] += gl[b] wg * x[b, K:], G[b, K:] += gl[b] wg * x[b, :K], one fma
+    per element (`lr_ncf_pair_bwd_f32`).  `B`: the first B rows (default: all of `gl`)."""
+    _req(x, torch.float32, "x", 2)
+    _req(G, torch.float32, "G", 2)
+    _req(gl, torch.float32, "gl", 1)
+    _req(wg, torch.float32, "wg")
+    K = _ncf_k(wg.numel())
+    B = gl.numel() if B is None else int(B)
+    if x.shape[1] != 2 * K or G.shape[1] != 2 * K or min(x.shape[0], G.shape[0], gl.numel()) < B:
+        raise ValueError("shape mismatch: x and G must be [>= B, 2K], gl [>= B], wg [K]")
+    _call("lr_ncf_pair_bwd_f32", _ptr(x), _ptr(gl), _ptr(wg), _ptr(G), B, K, _stream())
+    return G
+
+
+def _c_ints(values):
+    import ctypes as C
+
+    return (C.c_int * len(values))(*[int(v) for v in values])
+
+
+def ncf_score_supported(K: int, widths) -> bool:
+    """The envelope of `ncf_score` (`lr_ncf_score_supported`: K, the number of layers, the widths and the 160 KB of LDS)."""
+    widths = [int(w) for w in widths]
+    return bool(_lib.load().lr_ncf_score_supported(int(K), len(widths), _c_ints(widths)))
+
+
+def ncf_score(table: torch.Tensor, users: torch.Tensor, items: torch.Tensor, W, b, s, t, wg: torch.Tensor, wd: torch.Tensor,
+              c: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[p] = (u * i) . wg + h_L . wd + c for the pairs of global rows (users[p], items[p]) in one launch, with
+    h_l = relu(h_{l-1} @ W[l] + b[l]) * s[l] + t[l] and a bare last layer (`lr_ncf_score_f32`).  `W`, `b`: one tensor per layer;
+    `s`, `t`: None, or one entry per layer (None: identity).  Outside the envelope (`ncf_score_supported`): ValueError."""
+    import ctypes as C
+
+    _req(table, torch.float32, "table", 2)
+    _req(users, torch.int32, "users", 1)
+    _req(items, torch.int32, "items", 1)
+    V, K = table.shape
+    L, n = len(W), users.numel()
+    if items.numel() != n or len(b) != L or (s is None) != (t is None) or (s is not None and (len(s) != L or len(t) != L)):
+        raise ValueError("shape mismatch: one user and one item per pair, one W, b (and s, t) per layer")
+    widths, d_in = [], 2 * K
+    for l in range(L):
+        _req(W[l], torch.float32, f"W[{l}]", 2)
+        _req(b[l], torch.float32, f"b[{l}]", 1)
+        if W[l].shape[0] != d_in or b[l].numel() != W[l].shape[1]:
+            raise ValueError(f"shape mismatch: W[{l}] must be [{d_in}, width] and b[{l}] [width]")
+        for name, a in (("s", s), ("t", t)):
+            if a is not None and a[l] is not None and _req(a[l], torch.float32, f"{name}[{l}]", 1).numel() != W[l].shape[1]:
+                raise ValueError(f"shape mismatch: {name}[{l}] must be [width]")
+        if s is not None and (s[l] is None) != (t[l] is None):
+            raise ValueError(f"s[{l}] and t[{l}] must be given together")
+        d_in = W[l].shape[1]
+        widths.append(d_in)
+    _req(wg, torch.float32, "wg")
+    _req(wd, torch.float32, "wd")
+    if wg.numel() != K or wd.numel() != d_in:
+        raise ValueError("shape mismatch: wg must be [K] and wd [widths[-1]]")
+    out = torch.empty(n, dtype=torch.float32, device=table.device) if out is None else _req(out, torch.float32, "out", 1)
+    if out.numel() < n:
+        raise ValueError("shape mismatch: out must hold one score per pair")
+    ptrs = lambda a: None if a is None else (C.c_void_p * L)(*[_ptr(x) or None for x in a])
+    _call("lr_ncf_score_f32", _ptr(table), V, K, _ptr(users), _ptr(items), n, L, _c_ints(widths), ptrs(W), ptrs(b), ptrs(s), ptrs(t),
+          _ptr(wg), _ptr(wd), float(c), _ptr(out), _stream())
+    return out
+
+
+# --------------------------------------------------------------------------------------
 # FM
 # --------------------------------------------------------------------------------------
 def fm_pairwise_fwd(e: torch.Tensor, want_sum: bool = True):
