@@ -938,6 +938,51 @@ int lr_cf_predict_f32(const int32_t* srow, const int32_t* irow, int64_t n, const
                       lr_stream_t stream);
 
 /* ----------------------------------------------------------------------------------
+ * RsUserCF / RsItemCF (csrc/cf_sim.hip, csrc/cf_state.hip) — replace the engine of the reference's incremental
+ * neighbourhood models: rust/src/similarities.rs:13-180 (compute_sum_squares, invert_cosine), incremental.rs:9-115
+ * (update_sum_squares, update_cosine, accumulate_cosine) and the predict of item_cf.rs:118-153 / user_cf.rs:113-148 with
+ * inference.rs:11-71.  The state of n_x rows is a symmetric CSR without diagonal (int64 rowptr, int32 ascending col) of
+ * every pair with a count above 0, carrying prod f32, cnt int32 and sim f32, and sumsq f32 [n_x].  No floating-point
+ * atomics anywhere: identical bits run to run.
+ *   lr_cf_pair_state_f32   the accumulation of lr_cf_sim_f32 (same X / Y, work items, passes and workspace,
+ *                         lr_cf_sim_ws_bytes) with another epilogue: every column whose count of shared y is above 0 is
+ *                         written with its product sum (out_prod, ascending y, unfused multiply and add) and its count
+ *                         (out_cnt), a sum of exactly 0 included; nothing is normalised.
+ *   lr_cf_sumsq_f32       out[r] = s (accumulate 0) or out[r] + s (accumulate != 0, one f32 add), s the sequential f32 fold
+ *                         from 0 of val * val over CSR row r in stored (ascending column) order; out f32 [n_rows].
+ *   lr_cf_state_merge_f32 the row-wise union of the old state (o_*, o_nnz entries) and a delta (d_*, d_nnz entries, from
+ *                         lr_cf_pair_state_f32), both over n_x rows (the caller pads the old rowptr for new rows).  Pass 0
+ *                         writes is_new (uint8 [d_nnz]): 1 where the old row lacks the delta entry's column.  Pass 1 takes
+ *                         rank (int64 [d_nnz + 1], the exclusive scan of is_new with the total last) and writes the
+ *                         o_nnz + rank[d_nnz] entries of the union in row order with ascending columns: a pair of the
+ *                         delta gets prod = old + delta (the delta alone if new), cnt = old + delta and
+ *                         sim = prod / (sqrt(sumsq[x1]) * sqrt(sumsq[x2])), correctly rounded, 0 if prod or either sum
+ *                         is 0; every other pair keeps its three values bit for bit.  The new rowptr is
+ *                         o_ptr + rank[d_ptr] (the caller's).  Entries, not rows, are spread over the workgroups, so
+ *                         rows of any length are handled alike.  Columns must be below n_x.
+ *   lr_cf_predict_topk_f32   for every pair q the first min(k, tk_len) entries of the top-k list of row srow[q] (tk_*, as
+ *                         written by lr_cf_topk_f32) that the sorted interaction row irow[q] holds, whatever their
+ *                         label: ranking (rating 0) S / n with S the sequential f32 sum of the hit sims in list order,
+ *                         rating the sequential sum of (label * sim) / S; unclipped.  none[q] = 1 and pred[q] =
+ *                         default_pred where there is no hit. */
+int lr_cf_pair_state_f32(const int64_t* x_ptr, const int32_t* x_col, const float* x_val, const int64_t* y_ptr,
+                         const int32_t* y_col, const float* y_val, int64_t n_x, const int32_t* item_row,
+                         const int32_t* item_tile, const int32_t* order, int64_t n_items, int pass, int64_t* item_nnz,
+                         const int64_t* item_off, int32_t* out_col, float* out_prod, int32_t* out_cnt, void* ws,
+                         size_t ws_bytes, lr_stream_t stream);
+int lr_cf_sumsq_f32(const int64_t* ptr, const float* val, int64_t n_rows, int accumulate, float* out,
+                    lr_stream_t stream);
+int lr_cf_state_merge_f32(const int64_t* o_ptr, const int32_t* o_col, const float* o_prod, const int32_t* o_cnt,
+                          const float* o_sim, int64_t o_nnz, const int64_t* d_ptr, const int32_t* d_col,
+                          const float* d_prod, const int32_t* d_cnt, int64_t d_nnz, int64_t n_x, const float* sumsq,
+                          int pass, uint8_t* is_new, const int64_t* rank, int32_t* out_col, float* out_prod,
+                          int32_t* out_cnt, float* out_sim, lr_stream_t stream);
+int lr_cf_predict_topk_f32(const int32_t* srow, const int32_t* irow, int64_t n, const int32_t* tk_ids,
+                           const float* tk_sims, const int32_t* tk_len, int64_t tk_k, int64_t k, const int64_t* i_ptr,
+                           const int32_t* i_col, const float* i_val, int rating, float default_pred, float* pred,
+                           int32_t* none, lr_stream_t stream);
+
+/* ----------------------------------------------------------------------------------
  * Swing (csrc/swing.hip) — replaces the score engine of the reference's Swing model, rust/src/graph.rs:143-233
  * (compute_single_swing: every user pair of every item, the pair's term scattered over the pair's common items, with a
  * 100 M-entry cache of intersections and a thread pool; compute_swing_scores: the weights 1 / sqrt(|I_u|), :210-213).

@@ -211,6 +211,11 @@ SIGNATURES = {
     "lr_cf_recommend_f32": (_int, [_p, _i64, _int, _p, _p, _p, _p, _p, _p, _i64, _i64, _p, _p, _int, _i64, _p, _p, _p,
                                    _p, _p, _p, _sz, _p]),
     "lr_cf_predict_f32": (_int, [_p, _p, _i64, _p, _p, _p, _p, _p, _p, _i64, _int, _f32, _f32, _f32, _p, _p, _p]),
+    "lr_cf_pair_state_f32": (_int, [_p, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _i64, _int, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "lr_cf_sumsq_f32": (_int, [_p, _p, _i64, _int, _p, _p]),
+    "lr_cf_state_merge_f32": (_int, [_p, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _i64, _i64, _p, _int, _p, _p, _p, _p, _p, _p,
+                                     _p]),
+    "lr_cf_predict_topk_f32": (_int, [_p, _p, _i64, _p, _p, _p, _i64, _i64, _p, _p, _p, _int, _f32, _p, _p, _p]),
     "lr_swing_tile_cols": (_int, []),
     "lr_swing_lds_users": (_int, []),
     "lr_swing_pairs_ws_bytes": (_sz, []),

@@ -8,6 +8,7 @@ from .fm import FM, DeepFM
 from .graphsage import GraphSage
 from .item2vec import Item2Vec
 from .item_cf import ItemCF
+from .item_cf_rs import RsItemCF
 from .lightgcn import LightGCN
 from .ncf import NCF
 from .ngcf import NGCF
@@ -20,9 +21,10 @@ from .swing import Swing
 from .transformer import Transformer
 from .two_tower import TwoTower
 from .user_cf import UserCF
+from .user_cf_rs import RsUserCF
 from .wavenet import WaveNet
 from .wide_deep import WideDeep
 from .youtube_ranking import YouTubeRanking
 from .youtube_retrieval import YouTubeRetrieval
 
-__all__ = ["ALS", "AutoInt", "BPR", "Caser", "DIN", "DeepFM", "DeepWalk", "FM", "GraphSage", "Item2Vec", "ItemCF", "LightGCN", "NCF", "NGCF", "PinSage", "RNN4Rec", "SIM", "SVD", "SVDpp", "Swing", "Transformer", "TwoTower", "UserCF", "WaveNet", "WideDeep", "YouTubeRanking", "YouTubeRetrieval"]
+__all__ = ["ALS", "AutoInt", "BPR", "Caser", "DIN", "DeepFM", "DeepWalk", "FM", "GraphSage", "Item2Vec", "ItemCF", "LightGCN", "NCF", "NGCF", "PinSage", "RNN4Rec", "RsItemCF", "RsUserCF", "SIM", "SVD", "SVDpp", "Swing", "Transformer", "TwoTower", "UserCF", "WaveNet", "WideDeep", "YouTubeRanking", "YouTubeRetrieval"]

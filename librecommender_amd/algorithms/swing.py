@@ -19,36 +19,16 @@ import os
 
 import numpy as np
 import torch
-from scipy.sparse import csr_matrix
 from scipy.sparse import load_npz as load_sparse
 from scipy.sparse import save_npz as save_sparse
 
 from .. import ops
 from ..bases.base import hip_device
-from ..bases.cf_base import CfBase, _DeviceCsr
+from ..bases.cf_base import CfBase, _DeviceCsr, _resized, merge_interactions  # noqa: F401  (both are this module's names too)
 from ..evaluation.evaluate import print_metrics
 from ..recommendation import popular_recommendations
 from ..utils.misc import time_block
 from ..utils.validate import check_fitting
-
-
-def merge_interactions(old, new, shape):
-    """The union of two interaction CSRs with the labels of `new` winning (`CsrMatrix::merge`), shaped `shape`."""
-    old, new = old.tocoo(), new.tocoo()
-    ko = old.row.astype(np.int64) * shape[1] + old.col
-    kn = new.row.astype(np.int64) * shape[1] + new.col
-    keep = ~np.isin(ko, kn)
-    key = np.concatenate([ko[keep], kn])
-    val = np.concatenate([old.data[keep], new.data]).astype(np.float32)
-    m = csr_matrix((val, (key // shape[1], key % shape[1])), shape=shape, dtype=np.float32)
-    m.sort_indices()
-    return m
-
-
-def _resized(m, shape):
-    m = m.tocsr().copy()
-    m.resize(shape)
-    return m
 
 
 class Swing(CfBase):

@@ -66,6 +66,26 @@ def row_count(csr) -> np.ndarray:
     return np.diff(csr.indptr)
 
 
+def merge_interactions(old, new, shape):
+    """The union of two interaction CSRs with the labels of `new` winning (`CsrMatrix::merge`), shaped `shape`: what the
+    models that retrain on new data alone (Swing, RsUserCF, RsItemCF) keep for inference."""
+    old, new = old.tocoo(), new.tocoo()
+    ko = old.row.astype(np.int64) * shape[1] + old.col
+    kn = new.row.astype(np.int64) * shape[1] + new.col
+    keep = ~np.isin(ko, kn)
+    key = np.concatenate([ko[keep], kn])
+    val = np.concatenate([old.data[keep], new.data]).astype(np.float32)
+    m = csr_matrix((val, (key // shape[1], key % shape[1])), shape=shape, dtype=np.float32)
+    m.sort_indices()
+    return m
+
+
+def _resized(m, shape):
+    m = m.tocsr().copy()
+    m.resize(shape)
+    return m
+
+
 class _DeviceCsr:
     """A CSR on the device: rowptr int64, col int32 (ascending per row), val f32."""
 

@@ -9,6 +9,10 @@
 // and add: the reference's f32 order, with no atomics.  (x1, x2) and (x2, x1) get the same bits because the product is
 // commutative.  The count pass writes the nnz of every work item; the fill pass recomputes and writes the columns in
 // ascending order at the item's offset (an exclusive scan of the counts): the claim and the emit of tile_csr.hpp.
+//
+// The pair state of RsUserCF / RsItemCF (rust/src/similarities.rs:120-180, incremental.rs:24-73) is the same accumulation
+// with another epilogue (STATE): every column with a count above 0 is emitted with its product sum and its count, whatever
+// the sum is, and nothing is normalised.
 #include "tile_csr.hpp"
 
 // The reference rounds every product and every sum to f32 (no contraction into an FMA).  HIP's __fmul_rn / __fadd_rn are
@@ -52,6 +56,7 @@ struct SimArgs {
   const int64_t* item_off;
   int32_t* out_col;
   float* out_val;
+  int32_t* out_cnt;      // STATE only
   int* counter;
 };
 
@@ -69,7 +74,7 @@ __device__ __forceinline__ float pair_value(const SimArgs& a, int64_t x1, int64_
   return __fdiv_rn(prods, mul_rn(n1, n2));
 }
 
-template <int PASS>
+template <int PASS, bool STATE>
 __global__ __launch_bounds__(kSimThreads) void cf_sim_kernel(SimArgs a) {
   extern __shared__ __align__(16) unsigned char lds[];
   float* sP = reinterpret_cast<float*>(lds);
@@ -152,12 +157,22 @@ __global__ __launch_bounds__(kSimThreads) void cf_sim_kernel(SimArgs a) {
     }
     __syncthreads();
 
-    emit_tile<PASS, kSimThreads, kSimTile>(c0, c1, sWave, a.item_nnz, a.item_off, item, a.out_col, a.out_val,
-                                           [&](int64_t c, int idx, float* v) {
-                                             const float sim = pair_value(a, x1, c, sP[idx], sC[idx]);
-                                             if (v != nullptr) *v = sim;
-                                             return sim != 0.0f;
-                                           });
+    if constexpr (STATE) {
+      emit_tile_to<PASS, kSimThreads, kSimTile>(c0, c1, sWave, a.item_nnz, a.item_off, item,
+                                                [&](int64_t, int idx) { return sC[idx] > 0; },
+                                                [&](int64_t pos, int64_t c, int idx) {
+                                                  a.out_col[pos] = static_cast<int32_t>(c);
+                                                  a.out_val[pos] = sP[idx];
+                                                  a.out_cnt[pos] = sC[idx];
+                                                });
+    } else {
+      emit_tile<PASS, kSimThreads, kSimTile>(c0, c1, sWave, a.item_nnz, a.item_off, item, a.out_col, a.out_val,
+                                             [&](int64_t c, int idx, float* v) {
+                                               const float sim = pair_value(a, x1, c, sP[idx], sC[idx]);
+                                               if (v != nullptr) *v = sim;
+                                               return sim != 0.0f;
+                                             });
+    }
   }
 }
 
@@ -165,6 +180,22 @@ __global__ __launch_bounds__(kSimThreads) void cf_sim_kernel(SimArgs a) {
 }  // namespace lr
 
 using namespace lr;
+
+template <bool STATE>
+static int launch_sim(const SimArgs& a, int pass, lr_stream_t stream) {
+  hipStream_t s = as_stream(stream);
+  zero_words_async(a.counter, 1, s);
+  const int grid = static_cast<int>(a.n_items < 2 * kNumCU ? a.n_items : 2 * kNumCU);
+  int rc;
+  if (pass == 0) {
+    if ((rc = set_lds(cf_sim_kernel<0, STATE>, kSimLds)) != LR_OK) return rc;
+    hipLaunchKernelGGL((cf_sim_kernel<0, STATE>), dim3(grid), dim3(kSimThreads), kSimLds, s, a);
+  } else {
+    if ((rc = set_lds(cf_sim_kernel<1, STATE>, kSimLds)) != LR_OK) return rc;
+    hipLaunchKernelGGL((cf_sim_kernel<1, STATE>), dim3(grid), dim3(kSimThreads), kSimLds, s, a);
+  }
+  return launch_status();
+}
 
 extern "C" int lr_cf_sim_tile_cols(void) { return kSimTile; }
 
@@ -185,17 +216,21 @@ extern "C" int lr_cf_sim_f32(const int64_t* x_ptr, const int32_t* x_col, const f
   if ((pass == 0 && !item_nnz) || (pass == 1 && (!item_off || !out_col || !out_val))) return LR_EINVAL;
   if (ws == nullptr || ws_bytes < lr_cf_sim_ws_bytes()) return LR_EWORKSPACE;
   SimArgs a{x_ptr, x_col, x_val, y_ptr, y_col, y_val, n_x, norm, cnt, jac ? 1 : 0, min_common < 1 ? 1 : min_common,
-            item_row, item_tile, order, n_items, item_nnz, item_off, out_col, out_val, static_cast<int*>(ws)};
-  hipStream_t s = as_stream(stream);
-  zero_words_async(ws, 1, s);
-  const int grid = static_cast<int>(n_items < 2 * kNumCU ? n_items : 2 * kNumCU);
-  int rc;
-  if (pass == 0) {
-    if ((rc = set_lds(cf_sim_kernel<0>, kSimLds)) != LR_OK) return rc;
-    hipLaunchKernelGGL(cf_sim_kernel<0>, dim3(grid), dim3(kSimThreads), kSimLds, s, a);
-  } else {
-    if ((rc = set_lds(cf_sim_kernel<1>, kSimLds)) != LR_OK) return rc;
-    hipLaunchKernelGGL(cf_sim_kernel<1>, dim3(grid), dim3(kSimThreads), kSimLds, s, a);
-  }
-  return launch_status();
+            item_row, item_tile, order, n_items, item_nnz, item_off, out_col, out_val, nullptr, static_cast<int*>(ws)};
+  return launch_sim<false>(a, pass, stream);
+}
+
+extern "C" int lr_cf_pair_state_f32(const int64_t* x_ptr, const int32_t* x_col, const float* x_val, const int64_t* y_ptr,
+                                    const int32_t* y_col, const float* y_val, int64_t n_x, const int32_t* item_row,
+                                    const int32_t* item_tile, const int32_t* order, int64_t n_items, int pass,
+                                    int64_t* item_nnz, const int64_t* item_off, int32_t* out_col, float* out_prod,
+                                    int32_t* out_cnt, void* ws, size_t ws_bytes, lr_stream_t stream) {
+  if (n_x < 0 || n_x > INT32_MAX || n_items < 0 || (pass != 0 && pass != 1)) return LR_EINVAL;
+  if (n_items == 0) return LR_OK;
+  if (!x_ptr || !x_col || !x_val || !y_ptr || !y_col || !y_val || !item_row || !item_tile || !order) return LR_EINVAL;
+  if ((pass == 0 && !item_nnz) || (pass == 1 && (!item_off || !out_col || !out_prod || !out_cnt))) return LR_EINVAL;
+  if (ws == nullptr || ws_bytes < lr_cf_sim_ws_bytes()) return LR_EWORKSPACE;
+  SimArgs a{x_ptr, x_col, x_val, y_ptr, y_col, y_val, n_x, nullptr, nullptr, 0, 1,
+            item_row, item_tile, order, n_items, item_nnz, item_off, out_col, out_prod, out_cnt, static_cast<int*>(ws)};
+  return launch_sim<true>(a, pass, stream);
 }

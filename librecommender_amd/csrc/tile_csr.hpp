@@ -85,4 +85,42 @@ __device__ __forceinline__ void emit_tile(int64_t c0, int64_t c1, int64_t* sWave
   __syncthreads();
 }
 
+// The same emit for a caller that keeps more than one value per column (the pair state of cf_sim.hip): `keep(c, idx)`
+// says whether column c is kept, and in pass 1 `write(pos, c, idx)` stores it at position pos of the output, the item's
+// offset plus the number of kept columns below c.  Same conditions on entry and exit as emit_tile.
+template <int PASS, int THREADS, int TILE, typename Keep, typename Write>
+__device__ __forceinline__ void emit_tile_to(int64_t c0, int64_t c1, int64_t* sWave, int64_t* item_nnz,
+                                             const int64_t* item_off, int64_t item, Keep keep, Write write) {
+  constexpr int waves = THREADS / kWave, span = TILE / waves;
+  static_assert(THREADS % kWave == 0 && TILE % (waves * kWave) == 0, "a wave's span is whole rounds of 64 columns");
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+  const int64_t wb = c0 + static_cast<int64_t>(wave) * span;
+  int64_t kept = 0;
+  for (int r = 0; r < span; r += kWave) {
+    const int64_t c = wb + r + lane;
+    kept += __popcll(__ballot(c < c1 && keep(c, static_cast<int>(c - c0))));
+  }
+  if (lane == 0) sWave[wave] = kept;
+  __syncthreads();
+  if (PASS == 0) {
+    if (tid == 0) {
+      int64_t t = 0;
+      for (int w = 0; w < waves; ++w) t += sWave[w];
+      item_nnz[item] = t;
+    }
+  } else {
+    int64_t base = item_off[item];
+    for (int w = 0; w < wave; ++w) base += sWave[w];
+    const uint64_t below = (lane == 0) ? 0ull : (~0ull >> (kWave - lane));
+    for (int r = 0; r < span; r += kWave) {
+      const int64_t c = wb + r + lane;
+      const bool k = c < c1 && keep(c, static_cast<int>(c - c0));
+      const uint64_t m = __ballot(k);
+      if (k) write(base + __popcll(m & below), c, static_cast<int>(c - c0));
+      base += __popcll(m);
+    }
+  }
+  __syncthreads();
+}
+
 }  // namespace lr

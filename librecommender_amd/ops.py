@@ -9,7 +9,7 @@ from __future__ import annotations
 import os
 
 from dataclasses import dataclass
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -1760,35 +1760,57 @@ def _tile_work_items(n_rows: int, work: torch.Tensor, tmin: torch.Tensor, span: 
 
 
 def _two_pass_csr(fn: str, lead: tuple, rowptr: torch.Tensor, items, ws_bytes: int, cap: Optional[int], max_bytes,
-                  too_large: str, mark=lambda stage: None):
+                  too_large: str, mark=lambda stage: None, extra=(), entry_bytes: int = 8):
     """Count, scan, cap check, allocate, fill and rowptr of a two-pass kernel of csrc/tile_csr.hpp: `fn(*lead, item_row,
     item_tile, order, n_items, pass, item_nnz, item_off, col, val, ws, ws_bytes, stream)`.  Fills `rowptr` (zeros, int64
     [n_rows + 1]) and returns (rowptr, col, val); col and val are allocated only once the count pass has given their size
     (one host read), and a result above `cap` bytes (None: `_mem_cap(max_bytes)`, taken after the count pass) raises
-    MemoryError(too_large.format(total=, gib=, cap_gib=))."""
+    MemoryError(too_large.format(total=, gib=, cap_gib=)).  `extra`: dtypes of further per-entry outputs, passed behind
+    `val` and returned behind it; `entry_bytes`: what the cap check counts per entry."""
     item_row, item_tile, order, n_items = items
     dev = rowptr.device
     ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=dev)
     item_nnz = torch.zeros(n_items, dtype=torch.int64, device=dev)
     common = (*lead, _ptr(item_row), _ptr(item_tile), _ptr(order), n_items)
     mark("plan")
-    _call(fn, *common, 0, _ptr(item_nnz), 0, 0, 0, _ptr(ws), ws.numel(), _stream())
+    _call(fn, *common, 0, _ptr(item_nnz), 0, 0, 0, *(0 for _ in extra), _ptr(ws), ws.numel(), _stream())
     mark("count")
     item_end = torch.cumsum(item_nnz, 0)
     total = int(item_end[-1])
-    need = total * 8 + rowptr.numel() * 8
+    need = total * entry_bytes + rowptr.numel() * 8
     cap = _mem_cap(max_bytes, dev) if cap is None else int(cap)
     if need > cap:
         raise MemoryError(too_large.format(total=total, gib=need / 2**30, cap_gib=cap / 2**30))
     col = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
     val = torch.empty(max(total, 1), dtype=torch.float32, device=dev)
+    more = [torch.empty(max(total, 1), dtype=dt, device=dev) for dt in extra]
     item_off = (item_end - item_nnz).contiguous()
     mark("scan")
-    _call(fn, *common, 1, 0, _ptr(item_off), _ptr(col), _ptr(val), _ptr(ws), ws.numel(), _stream())
+    _call(fn, *common, 1, 0, _ptr(item_off), _ptr(col), _ptr(val), *(_ptr(t) for t in more), _ptr(ws), ws.numel(), _stream())
     rowptr[1:] = torch.cumsum(torch.zeros(rowptr.numel() - 1, dtype=torch.int64, device=dev).index_add_(
         0, item_row.to(torch.int64), item_nnz), 0)
     mark("fill")
-    return rowptr, col[:total], val[:total]
+    return (rowptr, col[:total], val[:total], *(t[:total] for t in more))
+
+
+def _cf_sim_items(x_ptr: torch.Tensor, x_col: torch.Tensor, y_ptr: torch.Tensor, y_col: torch.Tensor):
+    """The work items of the co-occurrence kernels of csrc/cf_sim.hip: (row, tile) over the tiles between the row's smallest
+    and largest co-occurring column."""
+    dev = x_ptr.device
+    n_x = x_ptr.numel() - 1
+    T = cf_sim_tile_cols()
+    nnz = x_col.numel()
+    deg_y = (y_ptr[1:] - y_ptr[:-1])
+    rows_x = torch.repeat_interleave(torch.arange(n_x, device=dev), x_ptr[1:] - x_ptr[:-1], output_size=nnz)
+    yc = x_col.to(torch.int64)
+    work = torch.zeros(n_x, dtype=torch.int64, device=dev).index_add_(0, rows_x, deg_y[yc])
+    first = y_col[y_ptr[:-1].clamp(max=max(y_col.numel() - 1, 0))].to(torch.int64) if y_col.numel() else deg_y
+    last = y_col[(y_ptr[1:] - 1).clamp(min=0)].to(torch.int64) if y_col.numel() else deg_y
+    tmin = torch.full((n_x,), n_x, dtype=torch.int64, device=dev).scatter_reduce_(0, rows_x, first[yc], "amin")
+    tmax = torch.full((n_x,), -1, dtype=torch.int64, device=dev).scatter_reduce_(0, rows_x, last[yc], "amax")
+    tmin, tmax = torch.div(tmin, T, rounding_mode="floor"), torch.div(tmax, T, rounding_mode="floor")
+    span = torch.where(work > 0, tmax - tmin + 1, torch.zeros_like(work))
+    return _tile_work_items(n_x, work, tmin, span)
 
 
 def cf_similarity(x_ptr: torch.Tensor, x_col: torch.Tensor, x_val: torch.Tensor, y_ptr: torch.Tensor,
@@ -1816,20 +1838,7 @@ def cf_similarity(x_ptr: torch.Tensor, x_col: torch.Tensor, x_val: torch.Tensor,
     n_x = x_ptr.numel() - 1
     if n_x > 2**31 - 1:
         raise ValueError("the similarity supports up to 2**31 - 1 rows")
-    T = cf_sim_tile_cols()
-    # work items: (row, tile) over the tiles between the row's smallest and largest co-occurring column
-    nnz = x_col.numel()
-    deg_y = (y_ptr[1:] - y_ptr[:-1])
-    rows_x = torch.repeat_interleave(torch.arange(n_x, device=dev), x_ptr[1:] - x_ptr[:-1], output_size=nnz)
-    yc = x_col.to(torch.int64)
-    work = torch.zeros(n_x, dtype=torch.int64, device=dev).index_add_(0, rows_x, deg_y[yc])
-    first = y_col[y_ptr[:-1].clamp(max=max(y_col.numel() - 1, 0))].to(torch.int64) if y_col.numel() else deg_y
-    last = y_col[(y_ptr[1:] - 1).clamp(min=0)].to(torch.int64) if y_col.numel() else deg_y
-    tmin = torch.full((n_x,), n_x, dtype=torch.int64, device=dev).scatter_reduce_(0, rows_x, first[yc], "amin")
-    tmax = torch.full((n_x,), -1, dtype=torch.int64, device=dev).scatter_reduce_(0, rows_x, last[yc], "amax")
-    tmin, tmax = torch.div(tmin, T, rounding_mode="floor"), torch.div(tmax, T, rounding_mode="floor")
-    span = torch.where(work > 0, tmax - tmin + 1, torch.zeros_like(work))
-    items = _tile_work_items(n_x, work, tmin, span)
+    items = _cf_sim_items(x_ptr, x_col, y_ptr, y_col)
     rowptr = torch.zeros(n_x + 1, dtype=torch.int64, device=dev)
     if items[3] == 0:
         return rowptr, torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.float32, device=dev)
@@ -1918,6 +1927,176 @@ def cf_predict(srow: torch.Tensor, irow: torch.Tensor, s_ptr: torch.Tensor, s_co
     _call("lr_cf_predict_f32", _ptr(srow), _ptr(irow), n, _ptr(s_ptr), _ptr(s_col), _ptr(s_val), _ptr(i_ptr),
           _ptr(i_col), _ptr(i_val), max(0, int(k)), 1 if rating else 0, float(lower), float(upper), float(default_pred),
           _ptr(pred), _ptr(none), _stream())
+    return pred, none
+
+
+# --------------------------------------------------------------------------------------
+# RsUserCF / RsItemCF (csrc/cf_sim.hip, csrc/cf_state.hip): the pair state and its incremental update
+# --------------------------------------------------------------------------------------
+CF_STATE_ENTRY_BYTES = 16    # col int32 + prod f32 + cnt int32 + sim f32: what the memory cap counts per entry of the state
+
+
+class CfState(NamedTuple):
+    """The state of n_x rows: a symmetric CSR without diagonal (ptr int64 [n_x + 1], col int32 ascending per row) of every
+    pair with a count above 0, with the accumulated product, the count and the cosine of its last refresh."""
+    ptr: torch.Tensor
+    col: torch.Tensor
+    prod: torch.Tensor
+    cnt: torch.Tensor
+    sim: torch.Tensor
+
+
+def cf_state_empty(n_x: int, device) -> CfState:
+    z = lambda dt: torch.zeros(0, dtype=dt, device=device)  # noqa: E731
+    return CfState(torch.zeros(int(n_x) + 1, dtype=torch.int64, device=device), z(torch.int32), z(torch.float32),
+                   z(torch.int32), z(torch.float32))
+
+
+def cf_pair_state(x_ptr: torch.Tensor, x_col: torch.Tensor, x_val: torch.Tensor, y_ptr: torch.Tensor, y_col: torch.Tensor,
+                  y_val: torch.Tensor, cap: Optional[int] = None):
+    """(rowptr int64 [n_x + 1], col int32 ascending per row, prod f32, cnt int32): every pair of rows of the forward CSR X
+    that shares a y of its inverted index Y, with the f32 sum of its products in ascending y (unfused multiply and add) and
+    the number of shared y; a sum of exactly 0 is kept (`invert_cosine` / `update_cosine` before the normalisation).  The
+    entries are counted before anything is allocated for them; above the memory cap (16 B per entry, what the state will
+    hold for them) the call raises MemoryError."""
+    _req(x_ptr, torch.int64, "x_ptr", 1)
+    _req(x_col, torch.int32, "x_col", 1)
+    _req(x_val, torch.float32, "x_val", 1)
+    _req(y_ptr, torch.int64, "y_ptr", 1)
+    _req(y_col, torch.int32, "y_col", 1)
+    _req(y_val, torch.float32, "y_val", 1)
+    if x_col.numel() != x_val.numel() or y_col.numel() != y_val.numel() or x_col.numel() != y_col.numel():
+        raise ValueError("X and Y must hold the same entries: one value per column, as many in Y as in X")
+    dev = x_ptr.device
+    n_x = x_ptr.numel() - 1
+    if n_x < 0 or y_ptr.numel() < 1:
+        raise ValueError("x_ptr and y_ptr must hold at least one element")
+    if n_x > 2**31 - 1:
+        raise ValueError("the pair state supports up to 2**31 - 1 rows")
+    items = _cf_sim_items(x_ptr, x_col, y_ptr, y_col) if n_x else (None, None, None, 0)
+    rowptr = torch.zeros(n_x + 1, dtype=torch.int64, device=dev)
+    if items[3] == 0:
+        e = cf_state_empty(n_x, dev)
+        return rowptr, e.col, e.prod, e.cnt
+    lead = (_ptr(x_ptr), _ptr(x_col), _ptr(x_val), _ptr(y_ptr), _ptr(y_col), _ptr(y_val), n_x)
+    return _two_pass_csr("lr_cf_pair_state_f32", lead, rowptr, items, _lib.load().lr_cf_sim_ws_bytes(), cap, CF_SIM_MAX_BYTES,
+                         "the pair state has {total} entries ({gib:.2f} GiB), above the {cap_gib:.2f} GiB that the device "
+                         "can hold for it; train on fewer rows", extra=(torch.int32,),
+                         entry_bytes=CF_STATE_ENTRY_BYTES)
+
+
+def cf_sumsq(ptr: torch.Tensor, val: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The f32 sum of squares of every CSR row as one sequential chain in stored order (`compute_sum_squares`).  With
+    `out` (f32 [n_rows]) the sums are added to it in place, one f32 add per row (`update_sum_squares`)."""
+    _req(ptr, torch.int64, "ptr", 1)
+    _req(val, torch.float32, "val", 1)
+    n = ptr.numel() - 1
+    if n < 0:
+        raise ValueError("ptr must hold at least one element")
+    if out is None:
+        res = torch.empty(n, dtype=torch.float32, device=ptr.device)
+    else:
+        res = _req(out, torch.float32, "out", 1)
+        if res.numel() != n:
+            raise ValueError(f"out must hold one sum per row ({n}), got {res.numel()}")
+    _call("lr_cf_sumsq_f32", _ptr(ptr), _ptr(val), n, 0 if out is None else 1, _ptr(res), _stream())
+    return res
+
+
+def cf_state_update(old: CfState, delta, sumsq: torch.Tensor, cap: Optional[int] = None) -> CfState:
+    """The state after adding `delta` (rowptr, col, prod, cnt of `cf_pair_state` on the new interactions, n_x rows) to
+    `old` (at most n_x rows; rows beyond its own are empty): the row-wise union, where a pair of the delta gets
+    prod = old + delta, cnt = old + delta and its cosine from `sumsq` (f32 [n_x], already updated), and every other pair
+    keeps its values bit for bit (`accumulate_cosine`).  Counted before it is allocated: above the memory cap (16 B per
+    entry) the call raises MemoryError."""
+    d_ptr, d_col, d_prod, d_cnt = delta
+    for t, dt, nm in ((old.ptr, torch.int64, "old.ptr"), (old.col, torch.int32, "old.col"),
+                      (old.prod, torch.float32, "old.prod"), (old.cnt, torch.int32, "old.cnt"),
+                      (old.sim, torch.float32, "old.sim"), (d_ptr, torch.int64, "delta rowptr"),
+                      (d_col, torch.int32, "delta col"), (d_prod, torch.float32, "delta prod"),
+                      (d_cnt, torch.int32, "delta cnt"), (sumsq, torch.float32, "sumsq")):
+        _req(t, dt, nm, 1)
+    dev = d_ptr.device
+    n_x = d_ptr.numel() - 1
+    o_nnz, d_nnz = old.col.numel(), d_col.numel()
+    if n_x < 0 or not 1 <= old.ptr.numel() <= n_x + 1:
+        raise ValueError("the old state must have at least 0 and at most as many rows as the delta")
+    if sumsq.numel() != n_x:
+        raise ValueError(f"sumsq must hold one sum per row ({n_x}), got {sumsq.numel()}")
+    if not (old.prod.numel() == old.cnt.numel() == old.sim.numel() == o_nnz) or not (d_prod.numel() == d_cnt.numel() == d_nnz):
+        raise ValueError("every value array must have one element per column")
+    if n_x > 2**31 - 1:
+        raise ValueError("the state supports up to 2**31 - 1 rows")
+    ends = [int(old.ptr[-1]), int(d_ptr[-1])] + [int(c.max()) if c.numel() else -1 for c in (old.col, d_col)]
+    if ends[0] != o_nnz or ends[1] != d_nnz or max(ends[2:]) >= n_x:
+        raise ValueError("a rowptr does not end at its number of entries, or a column is not below the number of rows")
+    o_ptr = old.ptr
+    if o_ptr.numel() < n_x + 1:      # rows beyond the old state are empty
+        o_ptr = torch.full((n_x + 1,), o_nnz, dtype=torch.int64, device=dev)
+        o_ptr[: old.ptr.numel()] = old.ptr
+    sides = (_ptr(o_ptr), _ptr(old.col), _ptr(old.prod), _ptr(old.cnt), _ptr(old.sim), o_nnz, _ptr(d_ptr), _ptr(d_col),
+             _ptr(d_prod), _ptr(d_cnt), d_nnz, n_x, _ptr(sumsq))
+    rank = torch.zeros(d_nnz + 1, dtype=torch.int64, device=dev)
+    if d_nnz:
+        is_new = torch.empty(d_nnz, dtype=torch.uint8, device=dev)
+        _call("lr_cf_state_merge_f32", *sides, 0, _ptr(is_new), 0, 0, 0, 0, 0, _stream())
+        torch.cumsum(is_new, 0, dtype=torch.int64, out=rank[1:])
+        del is_new
+    total = o_nnz + int(rank[-1])
+    need = total * CF_STATE_ENTRY_BYTES + (n_x + 1) * 8
+    cap = _mem_cap(CF_SIM_MAX_BYTES, dev) if cap is None else int(cap)
+    if need > cap:
+        raise MemoryError(f"the pair state has {total} entries ({need / 2**30:.2f} GiB), above the {cap / 2**30:.2f} GiB "
+                          "that the device can hold for it; train on fewer rows")
+    new = CfState(o_ptr + rank[d_ptr], torch.empty(total, dtype=torch.int32, device=dev),
+                  torch.empty(total, dtype=torch.float32, device=dev), torch.empty(total, dtype=torch.int32, device=dev),
+                  torch.empty(total, dtype=torch.float32, device=dev))
+    if total:
+        _call("lr_cf_state_merge_f32", *sides, 1, 0, _ptr(rank), _ptr(new.col), _ptr(new.prod), _ptr(new.cnt),
+              _ptr(new.sim), _stream())
+    return new
+
+
+def cf_state_visible(state: CfState, min_common: int):
+    """(rowptr, col, sim) of the pairs that ranking and prediction see: cnt >= min_common (`sort_by_sims` /
+    `update_by_sims`: counts only grow, so a pair enters once and is replaced whenever it is touched).  Values below 2
+    keep every pair and return the state's own arrays."""
+    if int(min_common) <= 1:
+        return state.ptr, state.col, state.sim
+    keep = state.cnt >= int(min_common)
+    below = torch.zeros(keep.numel() + 1, dtype=torch.int64, device=keep.device)
+    torch.cumsum(keep, 0, dtype=torch.int64, out=below[1:])
+    return below[state.ptr], state.col[keep].contiguous(), state.sim[keep].contiguous()
+
+
+def cf_predict_topk(srow: torch.Tensor, irow: torch.Tensor, tk_ids: torch.Tensor, tk_sims: torch.Tensor,
+                    tk_len: torch.Tensor, i_ptr: torch.Tensor, i_col: torch.Tensor, i_val: torch.Tensor, k: int,
+                    rating: bool, default_pred: float):
+    """Predictions of the pairs (srow[q], irow[q]) the way the reference's Rust models make them (`item_cf.rs:118-153`,
+    `compute_pred`): the top-k list of row srow[q] (`cf_topk`) is cut to k entries BEFORE it is intersected with the
+    interaction row irow[q]; every hit counts whatever its label; ranking S / n, rating sum((label * sim) / S), sequential
+    f32 sums in list order, unclipped.  Returns (pred f32 [n], none int32 [n]: 1 where there is no hit and pred is
+    default_pred)."""
+    for t, nm in ((srow, "srow"), (irow, "irow"), (i_col, "i_col"), (tk_len, "tk_len")):
+        _req(t, torch.int32, nm, 1)
+    _req(tk_ids, torch.int32, "tk_ids", 2)
+    _req(tk_sims, torch.float32, "tk_sims", 2)
+    _req(i_ptr, torch.int64, "i_ptr", 1)
+    _req(i_val, torch.float32, "i_val", 1)
+    if tk_ids.shape != tk_sims.shape or tk_len.numel() != tk_ids.shape[0] or tk_ids.shape[1] < 1:
+        raise ValueError("tk_ids and tk_sims must be [n_rows, k'] with k' >= 1 and tk_len [n_rows]")
+    if srow.numel() != irow.numel():
+        raise ValueError("srow and irow must name as many pairs")
+    if int(k) < 1:
+        raise ValueError("k must be at least 1")
+    if i_col.numel() != i_val.numel():
+        raise ValueError("i_col and i_val must have one element per entry")
+    n = srow.numel()
+    pred = torch.empty(n, dtype=torch.float32, device=srow.device)
+    none = torch.empty(n, dtype=torch.int32, device=srow.device)
+    _call("lr_cf_predict_topk_f32", _ptr(srow), _ptr(irow), n, _ptr(tk_ids), _ptr(tk_sims), _ptr(tk_len), tk_ids.shape[1],
+          int(k), _ptr(i_ptr), _ptr(i_col), _ptr(i_val), 1 if rating else 0, float(default_pred), _ptr(pred), _ptr(none),
+          _stream())
     return pred, none
 
 
