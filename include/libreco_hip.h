@@ -1468,6 +1468,40 @@ int lr_ncf_score_f32(const float* table, int64_t V, int K, const int32_t* users,
                      const int* widths, const float* const* W, const float* const* b, const float* const* s,
                      const float* const* t, const float* wg, const float* wd, float c, float* out, lr_stream_t stream);
 
+/* ---- IVF-Flat index (csrc/ivf.hip): inner-product inverted file over f32 rows ---------------------------------------------
+ * Rows, centroids and queries are [*, D] f32, D % 4 == 0, 4 <= D <= 256, 16-byte aligned; nlist <= 65536; fewer than 2^31 rows
+ * (LR_ESHAPE otherwise, nothing written).  No floating-point atomics anywhere: two calls give the same bits.
+ *
+ * lr_ivf_assign_f32: list_of[r] = the centroid of largest inner product with row r, ties to the lowest list id (a row whose
+ *   scores are all NaN goes to list 0); best_score (nullable) [n] = that inner product.
+ * lr_ivf_build_lists: stable counting sort of list_of (values in [0, nlist)) -> list_ptr int64 [nlist + 1] (CSR of the lists)
+ *   and list_ids int32 [n] (row ids, ascending within a list).  Integer work only.  The rows in list order are
+ *   lr_embed_gather_f32(rows, list_ids).  Workspace: lr_ivf_build_ws_bytes, 256-byte aligned.
+ * lr_ivf_centroids_f32: centroids[l] = (sum of rows[list_ids[p]] over list l, p ascending, in a fixed order) / f32(count), one
+ *   division per element; an empty list keeps its row of `centroids`.  `n` = list_ptr[nlist] entries, ids below n_rows.
+ *   Workspace: lr_ivf_centroids_ws_bytes, contents arbitrary.
+ * lr_ivf_search_f32: per query the `nprobe` lists of largest (inner product with the centroid desc, list id asc), found by
+ *   lr_score_topk_f32; among the rows of those lists (list_rows [N, D] = the catalogue in list order, list_ids their global ids)
+ *   the k largest by (score desc, global id asc), consumed ids of flagged queries dropped.  consumed_ptr / consumed_idx /
+ *   filter_flag and out_scores / out_ids [B, k] exactly as in lr_score_topk_f32 (id -1 / score -inf beyond the surviving
+ *   candidates).  Scores are f32 fma chains; no B x N block exists.  Envelope (lr_ivf_supported, the single source of truth):
+ *   D as above, 1 <= k <= 1024, 1 <= nprobe <= nlist <= min(N, 65536), nprobe within lr_score_topk_f32's k (4096), N < 2^31 and
+ *   at most 4 GiB of partial keys.  Workspace: lr_ivf_search_ws_bytes (0 outside the envelope), 256-byte aligned. */
+int lr_ivf_supported(int64_t B, int64_t N, int D, int k, int nprobe, int nlist);
+size_t lr_ivf_search_ws_bytes(int64_t B, int64_t N, int D, int k, int nprobe, int nlist);
+size_t lr_ivf_build_ws_bytes(int64_t n, int nlist);
+size_t lr_ivf_centroids_ws_bytes(int64_t n, int D);
+int lr_ivf_assign_f32(const float* rows, int64_t n, const float* centroids, int nlist, int D, int32_t* list_of,
+                      float* best_score /* [n] or NULL */, lr_stream_t stream);
+int lr_ivf_build_lists(const int32_t* list_of, int64_t n, int nlist, int64_t* list_ptr, int32_t* list_ids, void* ws,
+                       size_t ws_bytes, lr_stream_t stream);
+int lr_ivf_centroids_f32(const float* rows, int64_t n_rows, int D, const int64_t* list_ptr, const int32_t* list_ids, int64_t n,
+                         int nlist, float* centroids /* [nlist, D], in place */, void* ws, size_t ws_bytes, lr_stream_t stream);
+int lr_ivf_search_f32(const float* queries, int64_t B, const float* centroids, int nlist, const int64_t* list_ptr,
+                      const int32_t* list_ids, const float* list_rows, int64_t N, int D, const int64_t* consumed_ptr,
+                      const int32_t* consumed_idx, const uint8_t* filter_flag, int k, int nprobe, float* out_scores,
+                      int64_t* out_ids, void* ws, size_t ws_bytes, lr_stream_t stream);
+
 /* Measurement probe (scripts/mfma_peak.py): iters x 8 back-to-back v_mfma_f32_32x32x2_f32 per wave on
  * 256 x waves_per_simd workgroups — the f32 MFMA rate the chip sustains at the clock it holds under that load. */
 int lr_mfma_f32_probe(int iters, int waves_per_simd, float* out, lr_stream_t stream);

@@ -102,11 +102,13 @@ class EmbedBase(Base):
         return e if item is None else e[self.get_item_id(item)]
 
     # ---- nearest neighbours in embedding space (`embed_base.py:415-551`) ------------------------
-    def init_knn(self, approximate, sim_type, M=100, ef_construction=200, ef_search=200):
-        """Prepare `search_knn_users / search_knn_items`.  The search is always the exact
+    def init_knn(self, approximate, sim_type, M=100, ef_construction=200, ef_search=200, *, nlist=None, nprobe=None):
+        """Prepare `search_knn_users / search_knn_items`.  Without `nlist` the search is the exact
         full scan on the MFMA pipe (`lr_score_topk_f32` over unit-normalised rows for "cosine"):
-        there is no approximate index here, `approximate=True` (HNSW via nmslib in the reference)
-        is accepted and served exactly; `M / ef_construction / ef_search` are ignored."""
+        `approximate=True` (HNSW via nmslib in the reference) is accepted and served exactly;
+        `M / ef_construction / ef_search` are ignored.  With `nlist` both sides are searched through an
+        IVF-Flat index (`recommendation/ivf.py`) of `nlist` lists (at most the side's row
+        count) built over the same, possibly normalised, rows, `nprobe` (default 1) lists per query."""
         if sim_type == "cosine":
             self.include_bias = False
         elif sim_type == "inner-product":
@@ -121,6 +123,13 @@ class EmbedBase(Base):
                 e = e / torch.where(norm == 0, torch.ones_like(norm), norm)
             self._knn_rows[side] = e.contiguous()
         self.approximate, self.sim_type = approximate, sim_type
+        self._knn_index = {}
+        if nlist is not None:
+            from ..recommendation.ivf import IVFFlatIndex
+
+            for side, rows in self._knn_rows.items():
+                nl = min(int(nlist), rows.shape[0])
+                self._knn_index[side] = IVFFlatIndex.train_add(rows, nl, nprobe=min(int(nprobe or 1), nl))
 
     def _knn_topk(self, queries, rows, k):
         from .. import ops
@@ -128,6 +137,10 @@ class EmbedBase(Base):
 
     def _search_knn(self, side, inner, k):
         rows = self._knn_rows[side]
+        index = getattr(self, "_knn_index", {}).get(side)
+        if index is not None:
+            _, ids = index.search(rows[inner:inner + 1].contiguous(), k)
+            return [int(i) for i in ids[0].tolist() if i >= 0]
         _, ids = self._knn_topk(rows[inner:inner + 1].contiguous(), rows, k)
         return [int(i) for i in ids[0].tolist()]
 

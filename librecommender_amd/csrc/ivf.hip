@@ -1,0 +1,571 @@
+// Inverted-file (IVF-Flat) index over f32 rows, inner-product metric: deterministic k-means (assignment + per-list means), the
+// list build, and the search (coarse top-nprobe over the centroids, then a scan of the probed lists with fused filter and top-k).
+//
+// Decomposition
+//   assign    : ivf_assign_kernel.  A workgroup keeps 16 R rows in registers (16 lanes per row, each lane NCH 16-byte chunks; R rows
+//               per lane group) and streams ALL centroids through LDS in tiles of 32 KB; per (row, centroid) the 16 partial
+//               dot products are reduced with four DPP adds, and every lane of the group tracks the same (best score, lowest id).
+//               This is the VALU form (f32 fma per lane): the f32 MFMA form of the same loop is future work (profiles/ivf.md).
+//   lists     : stable radix sort of (list id, row id) pairs (rocPRIM, integer work only) gives list_ids ascending within a list;
+//               list_ptr is a lower bound of every list id in the sorted keys.  The row permutation is lr_embed_gather_f32.
+//   centroids : the entry stream (rows in list order) is cut into chunks of kIvfCH entries, one wave per chunk, so one huge list
+//               spreads over the chip.  A list that lies inside one chunk is summed and divided there; a list that crosses chunk
+//               borders leaves one partial sum per chunk and a second kernel adds them in chunk order (four interleaved slices,
+//               combined in slice order).  No floating-point atomics: the order of every sum is fixed by the shapes alone.
+//   search    : (1) coarse = lr_score_topk_f32(queries, centroids, k = nprobe): the nprobe best lists per query by (score desc,
+//               list id asc); (2) ivf_plan_kernel turns every (query, probed list) into ceil(len / CL) work items and scans the
+//               counts (one workgroup); (3) ivf_scan_kernel: a persistent grid of waves, one work item per wave at a time — the
+//               query sits in registers, list rows stream as float4 per lane (16 lanes per row, four rows per load), DPP reduce,
+//               survivors of the running threshold (and of the consumed filter) are appended to the wave's candidate list in LDS as
+//               64-bit (score, id) keys and the list is cut back to its k best by bisection when it fills (topk_keys.hpp); every
+//               work item leaves <= k keys; (4) ivf_merge_kernel: one workgroup per query streams its work items' keys through
+//               the same threshold / append / select scheme (one list per wave, then wave 0 folds the four) and sorts the k
+//               winners.  Order (score desc, id asc) is total, so the result does not depend on CL or on the grid.
+#include <cstring>
+
+#include <rocprim/rocprim.hpp>
+
+#include "common.hpp"
+#include "topk_keys.hpp"
+
+namespace lr {
+
+constexpr int kIvfCH = 1024;               // entries per chunk of the centroid sums
+constexpr int kIvfTileBytes = 32 * 1024;   // centroid tile of the assignment in LDS
+constexpr int kIvfMinCL = 64;              // shortest chunk of a list one search work item takes
+constexpr int64_t kIvfSpread = int64_t(1) << 17;   // a whole-catalogue list is cut into about this many chunks (over all queries)
+constexpr size_t kIvfMaxPartBytes = size_t(4) << 30;   // partial top-k keys the search may ask for
+
+static inline size_t ivf_al(size_t x) { return (x + 255) / 256 * 256; }
+
+template <int CTRL>
+__device__ __forceinline__ float ivf_dpp_add(float v) {
+  return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
+}
+// sum over the 16 lanes of a DPP row, the same bits on each of them (every step adds a pair in both orders)
+__device__ __forceinline__ float row16_sum(float v) {
+  v = ivf_dpp_add<0xB1>(v);    // quad_perm [1,0,3,2]
+  v = ivf_dpp_add<0x4E>(v);    // quad_perm [2,3,0,1]
+  v = ivf_dpp_add<0x141>(v);   // row_half_mirror
+  v = ivf_dpp_add<0x140>(v);   // row_mirror
+  return v;
+}
+__device__ __forceinline__ float dot4(float4 a, float4 b, float p) {
+  p = fmaf(a.x, b.x, p);
+  p = fmaf(a.y, b.y, p);
+  p = fmaf(a.z, b.z, p);
+  return fmaf(a.w, b.w, p);
+}
+
+// ---- assignment ---------------------------------------------------------------------------------------------------------------
+template <int NCH, int R>
+__global__ __launch_bounds__(kBlock) void ivf_assign_kernel(const float* __restrict__ rows, int64_t n,
+                                                            const float* __restrict__ cent, int nlist, int D, int TC,
+                                                            int32_t* __restrict__ list_of, float* __restrict__ best_out) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float4* s_c = reinterpret_cast<float4*>(smem);      // [TC][NCH * 16] chunks, zero beyond D
+  constexpr int W = NCH * 16;
+  const int tid = threadIdx.x, j = tid & 15, grp = tid >> 4;
+  const int D4 = D >> 2;
+  constexpr int ROWS = 16 * R;
+  for (int64_t t0 = static_cast<int64_t>(blockIdx.x) * ROWS; t0 < n; t0 += static_cast<int64_t>(gridDim.x) * ROWS) {
+    float4 x[R][NCH];
+    float best[R];
+    int bi[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int64_t row = t0 + grp * R + r;
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        const int ch = j + 16 * c;
+        x[r][c] = (row < n && ch < D4) ? ld4(rows + row * D + ch * 4) : f4_zero();
+      }
+      best[r] = -INFINITY;
+      bi[r] = 0;
+    }
+    for (int c0 = 0; c0 < nlist; c0 += TC) {
+      const int tc = nlist - c0 < TC ? nlist - c0 : TC;
+      __syncthreads();      // the previous tile has been read
+      for (int q = tid; q < tc * W; q += kBlock) {
+        const int cc = q / W, ch = q - cc * W;
+        s_c[q] = ch < D4 ? ld4(cent + static_cast<int64_t>(c0 + cc) * D + ch * 4) : f4_zero();
+      }
+      __syncthreads();
+      for (int cc = 0; cc < tc; ++cc) {
+        float4 cv[NCH];
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) cv[c] = s_c[cc * W + j + 16 * c];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          float p = 0.f;
+#pragma unroll
+          for (int c = 0; c < NCH; ++c) p = dot4(x[r][c], cv[c], p);
+          p = row16_sum(p);
+          if (p > best[r]) {      // strict: ties stay with the lowest list id
+            best[r] = p;
+            bi[r] = c0 + cc;
+          }
+        }
+      }
+    }
+    if (j == 0) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const int64_t row = t0 + grp * R + r;
+        if (row < n) {
+          list_of[row] = bi[r];
+          if (best_out != nullptr) best_out[row] = best[r];
+        }
+      }
+    }
+  }
+}
+
+// ---- list build ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void ivf_list_ptr_kernel(const int32_t* __restrict__ sorted, int64_t n, int nlist,
+                                                              int64_t* __restrict__ list_ptr) {
+  for (int l = blockIdx.x * kBlock + threadIdx.x; l <= nlist; l += gridDim.x * kBlock)
+    list_ptr[l] = lower_bound_i32(sorted, 0, n, l);
+}
+
+// ---- centroid means -----------------------------------------------------------------------------------------------------------
+// part[(c * 2 + 0) * D ..]: chunk c's sum of the list that began before the chunk; [(c * 2 + 1) * D ..]: of the list that begins
+// inside it and runs on past its end.
+__global__ __launch_bounds__(kBlock) void ivf_centroid_chunk_kernel(const float* __restrict__ rows, int D,
+                                                                    const int64_t* __restrict__ list_ptr,
+                                                                    const int32_t* __restrict__ list_ids, int64_t n, int nlist,
+                                                                    int64_t n_rows, float* __restrict__ cent,
+                                                                    float* __restrict__ part) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int D4 = D >> 2;
+  const int64_t nchunk = ceil_div(n, kIvfCH);
+  const int64_t nwaves = static_cast<int64_t>(gridDim.x) * (kBlock / kWave);
+  for (int64_t c = static_cast<int64_t>(blockIdx.x) * (kBlock / kWave) + (threadIdx.x >> 6); c < nchunk; c += nwaves) {
+    const int64_t p0 = c * kIvfCH, p1 = p0 + kIvfCH < n ? p0 + kIvfCH : n;
+    int lo = 0, hi = nlist - 1;      // the list of entry p0: the first l with list_ptr[l + 1] > p0
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (list_ptr[mid + 1] > p0) hi = mid; else lo = mid + 1;
+    }
+    int l = lo;
+    int64_t p = p0;
+    while (p < p1 && l < nlist) {
+      const int64_t ls = list_ptr[l], le = list_ptr[l + 1];
+      if (le <= p) {      // an empty list
+        ++l;
+        continue;
+      }
+      const int64_t e = le < p1 ? le : p1;
+      float4 acc = f4_zero();
+#pragma unroll 4
+      for (int64_t q = p; q < e; ++q) {
+        const int64_t id = list_ids[q];
+        if (lane < D4 && id >= 0 && id < n_rows) acc = f4_add(acc, ld4(rows + id * D + lane * 4));
+      }
+      const bool before = ls < p0, after = le > p1;
+      if (lane < D4) {
+        if (!before && !after) {
+          const float cnt = static_cast<float>(le - ls);
+          st4(cent + static_cast<int64_t>(l) * D + lane * 4, make_float4(acc.x / cnt, acc.y / cnt, acc.z / cnt, acc.w / cnt));
+        } else {
+          st4(part + (c * 2 + (before ? 0 : 1)) * D + lane * 4, acc);
+        }
+      }
+      p = e;
+    }
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void ivf_centroid_fold_kernel(int D, const int64_t* __restrict__ list_ptr, int nlist,
+                                                                   float* __restrict__ cent, const float* __restrict__ part) {
+  __shared__ float4 s_red[4][kWave];
+  const int col = threadIdx.x & (kWave - 1), slice = threadIdx.x >> 6;
+  const int D4 = D >> 2;
+  for (int l = blockIdx.x; l < nlist; l += gridDim.x) {
+    const int64_t ls = list_ptr[l], le = list_ptr[l + 1];
+    if (le <= ls) continue;
+    const int64_t c0 = ls / kIvfCH, c1 = (le - 1) / kIvfCH;
+    if (c0 == c1) continue;      // summed and divided by the chunk kernel
+    float4 acc = f4_zero();
+    if (col < D4)
+      for (int64_t i = slice; i <= c1 - c0; i += 4)
+        acc = f4_add(acc, ld4(part + ((c0 + i) * 2 + (i == 0 ? 1 : 0)) * D + col * 4));
+    s_red[slice][col] = acc;
+    __syncthreads();
+    if (slice == 0 && col < D4) {
+      const float4 t = f4_add(f4_add(f4_add(s_red[0][col], s_red[1][col]), s_red[2][col]), s_red[3][col]);
+      const float cnt = static_cast<float>(le - ls);
+      st4(cent + static_cast<int64_t>(l) * D + col * 4, make_float4(t.x / cnt, t.y / cnt, t.z / cnt, t.w / cnt));
+    }
+    __syncthreads();
+  }
+}
+
+// ---- search -------------------------------------------------------------------------------------------------------------------
+struct IvfPlan {
+  bool ok;
+  int CL;            // rows per work item
+  int C;             // candidate-list capacity of a wave (keys in LDS)
+  int K2;            // next_pow2(k): the final sort
+  int64_t P;         // B * nprobe (query, probed list) pairs
+  int64_t Wmax;      // work items at most
+  size_t off_cs, off_ci, off_pref, off_cnt, off_keys, off_coarse, coarse_bytes, total;
+};
+
+static inline int ivf_pow2(int x) {
+  int p = 2;
+  while (p < x) p <<= 1;
+  return p;
+}
+
+static IvfPlan ivf_plan(int64_t B, int64_t N, int D, int k, int nprobe, int nlist) {
+  IvfPlan p{};
+  p.ok = false;
+  if (B < 1 || N < 1 || N >= (int64_t(1) << 31) || D < 4 || D > 256 || (D % 4) != 0 || k < 1 || k > 1024 || nlist < 1 ||
+      nlist > 65536 || nprobe < 1 || nprobe > nlist || nlist > N)
+    return p;
+  p.coarse_bytes = lr_score_topk_ws_bytes(B, nlist, D, nprobe);      // the coarse kernel's own envelope (nprobe <= 4096)
+  if (p.coarse_bytes == 0) return p;
+  const int64_t cl = ceil_div(N * B, kIvfSpread);
+  p.CL = static_cast<int>(ceil_div(cl < kIvfMinCL ? kIvfMinCL : cl, 64) * 64);
+  p.K2 = ivf_pow2(k);
+  const int c = static_cast<int>(ceil_div(k + 256, 64) * 64);
+  p.C = c > p.K2 ? c : p.K2;
+  p.P = B * nprobe;
+  p.Wmax = B * (nprobe + ceil_div(N, p.CL));      // per query: sum of ceil(len / CL) over distinct lists <= nprobe + N / CL
+  if (p.P + 1 >= (int64_t(1) << 31) || p.Wmax >= (int64_t(1) << 31)) return p;
+  const size_t key_bytes = static_cast<size_t>(p.Wmax) * k * sizeof(uint64_t);
+  if (key_bytes > kIvfMaxPartBytes) return p;
+  size_t o = 0;
+  p.off_cs = o; o += ivf_al(static_cast<size_t>(p.P) * sizeof(float));
+  p.off_ci = o; o += ivf_al(static_cast<size_t>(p.P) * sizeof(int64_t));
+  p.off_pref = o; o += ivf_al(static_cast<size_t>(p.P + 1) * sizeof(int32_t));
+  p.off_cnt = o; o += ivf_al(static_cast<size_t>(p.Wmax) * sizeof(int32_t));
+  p.off_keys = o; o += ivf_al(key_bytes);
+  p.off_coarse = o; o += ivf_al(p.coarse_bytes);
+  p.total = o;
+  p.ok = true;
+  return p;
+}
+
+__device__ __forceinline__ int ivf_chunks_of(int64_t l, const int64_t* __restrict__ list_ptr, int nlist, int CL) {
+  if (l < 0 || l >= nlist) return 0;
+  return static_cast<int>((list_ptr[l + 1] - list_ptr[l] + CL - 1) / CL);
+}
+
+// pref[i] = work items before pair i, pref[P] = their total.  One workgroup: thread t takes a contiguous span of pairs.
+__global__ __launch_bounds__(1024) void ivf_plan_kernel(const int64_t* __restrict__ coarse_ids, int64_t P,
+                                                        const int64_t* __restrict__ list_ptr, int nlist, int CL,
+                                                        int32_t* __restrict__ pref) {
+  __shared__ int s_sum[1024];
+  const int tid = threadIdx.x;
+  const int64_t per = ceil_div(P, 1024);
+  const int64_t a = tid * per < P ? tid * per : P, b = a + per < P ? a + per : P;
+  int sum = 0;
+  for (int64_t i = a; i < b; ++i) sum += ivf_chunks_of(coarse_ids[i], list_ptr, nlist, CL);
+  s_sum[tid] = sum;
+  __syncthreads();
+  for (int off = 1; off < 1024; off <<= 1) {
+    const int v = tid >= off ? s_sum[tid - off] : 0;
+    __syncthreads();
+    s_sum[tid] += v;
+    __syncthreads();
+  }
+  int base = s_sum[tid] - sum;
+  for (int64_t i = a; i < b; ++i) {
+    pref[i] = base;
+    base += ivf_chunks_of(coarse_ids[i], list_ptr, nlist, CL);
+  }
+  if (tid == 1023) pref[P] = s_sum[1023];
+}
+
+// one wave's running top-k over a stream of keys: L[0..cnt) in LDS, T the threshold below which nothing can enter any more
+struct WaveTopk {
+  uint64_t* L;
+  int cnt, k, C, lane;
+  uint64_t T;
+  __device__ __forceinline__ void shrink() {
+    T = wave_select_kth(L, cnt, k, lane);
+    cnt = wave_compact(L, cnt, T, lane);
+    if (cnt > k) cnt = k;      // keys are distinct for a well-formed index: only duplicate ids could leave more
+  }
+  // every lane calls; at most `room` lanes pass per call and cnt + room <= C holds on entry
+  __device__ __forceinline__ void push(bool pass, uint64_t key) {
+    const uint64_t mask = __ballot(pass);
+    if (pass) L[cnt + __popcll(mask & ((1ull << lane) - 1ull))] = key;
+    cnt += __popcll(mask);
+  }
+};
+
+template <int NCH>
+__global__ __launch_bounds__(kBlock) void ivf_scan_kernel(
+    const float* __restrict__ queries, int D, const int64_t* __restrict__ coarse_ids, int nprobe, int64_t P,
+    const int32_t* __restrict__ pref, const int64_t* __restrict__ list_ptr, const int32_t* __restrict__ list_ids,
+    const float* __restrict__ list_rows, const int64_t* __restrict__ consumed_ptr, const int32_t* __restrict__ consumed_idx,
+    const uint8_t* __restrict__ filter_flag, int k, int C, int CL, int64_t Wmax, uint64_t* __restrict__ part_keys,
+    int32_t* __restrict__ part_cnt) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wid = tid >> 6, j = lane & 15, g = lane >> 4;
+  const int D4 = D >> 2;
+  WaveTopk tk;
+  tk.L = reinterpret_cast<uint64_t*>(smem) + static_cast<size_t>(wid) * C;
+  tk.k = k;
+  tk.C = C;
+  tk.lane = lane;
+  const int64_t total = pref[P] < Wmax ? pref[P] : Wmax;      // (Wmax bounds it for every well-formed index)
+  for (int64_t w = static_cast<int64_t>(blockIdx.x) * 4 + wid; w < total; w += static_cast<int64_t>(gridDim.x) * 4) {
+    int64_t lo = 0, hi = P - 1;      // the pair of work item w: pref[pair] <= w < pref[pair + 1]
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (pref[mid + 1] > w) hi = mid; else lo = mid + 1;
+    }
+    const int64_t pair = lo, q = pair / nprobe, l = coarse_ids[pair];
+    const int64_t r0 = list_ptr[l] + (w - pref[pair]) * CL;
+    const int64_t r1 = list_ptr[l + 1] < r0 + CL ? list_ptr[l + 1] : r0 + CL;
+    float4 qv[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) qv[c] = (j + 16 * c) < D4 ? ld4(queries + q * D + (j + 16 * c) * 4) : f4_zero();
+    const bool flt = consumed_ptr != nullptr && (filter_flag == nullptr || filter_flag[q] != 0);
+    const int64_t clo = flt ? consumed_ptr[q] : 0, chi = flt ? consumed_ptr[q + 1] : 0;
+    tk.cnt = 0;
+    tk.T = 0ull;
+    for (int64_t r = r0; r < r1; r += 16) {
+      float sc[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int64_t row = r + u * 4 + g;
+        float p = 0.f;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+          const int ch = j + 16 * c;
+          const float4 v = (row < r1 && ch < D4) ? ld4(list_rows + row * D + ch * 4) : f4_zero();
+          p = dot4(v, qv[c], p);
+        }
+        sc[u] = row16_sum(p);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int64_t row = r + u * 4 + g;
+        const bool ok = j == 0 && row < r1 && sc[u] == sc[u];      // NaN scores are dropped
+        const int32_t id = ok ? list_ids[row] : 0;
+        const uint64_t key = make_key(sc[u], static_cast<uint32_t>(id));
+        bool pass = ok && key > tk.T;
+        if (pass && flt) pass = !is_consumed(consumed_idx, clo, chi, id);
+        tk.push(pass, key);
+      }
+      if (tk.cnt + 16 > C) tk.shrink();
+    }
+    if (tk.cnt > k) tk.shrink();
+    for (int i = lane; i < tk.cnt; i += kWave) part_keys[w * k + i] = tk.L[i];
+    if (lane == 0) part_cnt[w] = tk.cnt;
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void ivf_merge_kernel(const int32_t* __restrict__ pref, int nprobe,
+                                                           const uint64_t* __restrict__ part_keys,
+                                                           const int32_t* __restrict__ part_cnt, int k, int C, int K2, int64_t Wmax,
+                                                           float* __restrict__ out_scores, int64_t* __restrict__ out_ids) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  uint64_t* s_keys = reinterpret_cast<uint64_t*>(smem);                       // [4][C]
+  int* s_cnt = reinterpret_cast<int*>(s_keys + static_cast<size_t>(4) * C);   // [4]
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wid = tid >> 6;
+  const int64_t u = blockIdx.x;
+  const int64_t w0 = pref[u * nprobe], w1 = pref[(u + 1) * nprobe] < Wmax ? pref[(u + 1) * nprobe] : Wmax;
+  WaveTopk tk;
+  tk.L = s_keys + static_cast<size_t>(wid) * C;
+  tk.k = k;
+  tk.C = C;
+  tk.lane = lane;
+  tk.cnt = 0;
+  tk.T = 0ull;
+  for (int64_t w = w0 + wid; w < w1; w += 4) {
+    const int n = part_cnt[w];
+    for (int i0 = 0; i0 < n; i0 += kWave) {
+      const int i = i0 + lane;
+      const uint64_t key = i < n ? part_keys[w * k + i] : 0ull;
+      tk.push(i < n && key > tk.T, key);
+      if (tk.cnt + kWave > C) tk.shrink();
+    }
+  }
+  if (tk.cnt > k) tk.shrink();
+  if (lane == 0) s_cnt[wid] = tk.cnt;
+  __syncthreads();
+  if (wid == 0) {
+    for (int o = 1; o < 4; ++o) {
+      const int n = s_cnt[o];
+      const uint64_t* src = s_keys + static_cast<size_t>(o) * C;
+      for (int i0 = 0; i0 < n; i0 += kWave) {
+        const int i = i0 + lane;
+        const uint64_t key = i < n ? src[i] : 0ull;
+        tk.push(i < n && key > tk.T, key);
+        if (tk.cnt + kWave > C) tk.shrink();
+      }
+    }
+    if (tk.cnt > k) tk.shrink();
+    for (int i = tk.cnt + lane; i < K2; i += kWave) tk.L[i] = 0ull;
+  }
+  __syncthreads();
+  uint64_t* a = s_keys;
+  for (int size = 2; size <= K2; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int t = tid; t < K2 / 2; t += kBlock) {
+        const int lo = 2 * t - (t & (stride - 1));
+        const int hi = lo + stride;
+        const bool desc = (lo & size) == 0;
+        const uint64_t x = a[lo], y = a[hi];
+        if (desc ? (x < y) : (x > y)) {
+          a[lo] = y;
+          a[hi] = x;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  for (int r = tid; r < k; r += kBlock) {
+    const uint64_t e = a[r];
+    if (e == 0ull) {
+      out_scores[u * k + r] = -INFINITY;
+      out_ids[u * k + r] = -1;
+    } else {
+      out_scores[u * k + r] = fkey_inv(static_cast<uint32_t>(e >> 32));
+      out_ids[u * k + r] = static_cast<int64_t>(0xFFFFFFFFu - static_cast<uint32_t>(e));
+    }
+  }
+}
+
+static inline bool ivf_row_shape_ok(int D) { return D >= 4 && D <= 256 && (D % 4) == 0; }
+static inline int ivf_key_bits(int nlist) {
+  int bits = 1;
+  while (bits < 31 && (int64_t(1) << bits) < nlist) ++bits;
+  return bits;
+}
+static inline size_t ivf_sort_scratch(int64_t n) { return ivf_al(static_cast<size_t>(n) * 8) * 2 + (size_t(8) << 20); }
+
+}  // namespace lr
+
+using namespace lr;
+
+extern "C" int lr_ivf_supported(int64_t B, int64_t N, int D, int k, int nprobe, int nlist) {
+  return ivf_plan(B, N, D, k, nprobe, nlist).ok ? 1 : 0;
+}
+
+extern "C" size_t lr_ivf_search_ws_bytes(int64_t B, int64_t N, int D, int k, int nprobe, int nlist) {
+  const IvfPlan p = ivf_plan(B, N, D, k, nprobe, nlist);
+  return p.ok ? p.total : 0;
+}
+
+extern "C" int lr_ivf_assign_f32(const float* rows, int64_t n, const float* centroids, int nlist, int D, int32_t* list_of,
+                                 float* best_score, lr_stream_t stream) {
+  LR_CHECK_ARG(n >= 0 && nlist >= 1);
+  if (!ivf_row_shape_ok(D) || nlist > 65536 || n >= (int64_t(1) << 31)) return LR_ESHAPE;
+  if (n == 0) return LR_OK;
+  LR_CHECK_ARG(rows && centroids && list_of);
+  LR_CHECK_ARG(reinterpret_cast<uintptr_t>(rows) % 16 == 0 && reinterpret_cast<uintptr_t>(centroids) % 16 == 0);
+  hipStream_t s = as_stream(stream);
+  const int nch = D <= 64 ? 1 : D <= 128 ? 2 : 4;
+  const int TC = kIvfTileBytes / (nch * 256);
+  const int rows_per_block = nch == 4 ? 64 : 128;
+  const dim3 grid(grid_for(n, rows_per_block)), block(kBlock);
+  if (nch == 1)
+    hipLaunchKernelGGL((ivf_assign_kernel<1, 8>), grid, block, kIvfTileBytes, s, rows, n, centroids, nlist, D, TC, list_of, best_score);
+  else if (nch == 2)
+    hipLaunchKernelGGL((ivf_assign_kernel<2, 8>), grid, block, kIvfTileBytes, s, rows, n, centroids, nlist, D, TC, list_of, best_score);
+  else
+    hipLaunchKernelGGL((ivf_assign_kernel<4, 4>), grid, block, kIvfTileBytes, s, rows, n, centroids, nlist, D, TC, list_of, best_score);
+  return launch_status();
+}
+
+extern "C" size_t lr_ivf_build_ws_bytes(int64_t n, int nlist) {
+  (void)nlist;
+  if (n < 0) n = 0;
+  return ivf_al(static_cast<size_t>(n) * 4) + ivf_sort_scratch(n);
+}
+
+extern "C" int lr_ivf_build_lists(const int32_t* list_of, int64_t n, int nlist, int64_t* list_ptr, int32_t* list_ids, void* ws,
+                                  size_t ws_bytes, lr_stream_t stream) {
+  LR_CHECK_ARG(n >= 0 && nlist >= 1 && list_ptr);
+  if (nlist > 65536 || n >= (int64_t(1) << 31)) return LR_ESHAPE;
+  hipStream_t s = as_stream(stream);
+  if (n > 0) {
+    LR_CHECK_ARG(list_of && list_ids && ws && reinterpret_cast<uintptr_t>(ws) % 256 == 0);
+    if (ws_bytes < lr_ivf_build_ws_bytes(n, nlist)) return LR_EWORKSPACE;
+    int32_t* sorted = static_cast<int32_t*>(ws);
+    char* prim = static_cast<char*>(ws) + ivf_al(static_cast<size_t>(n) * 4);
+    const size_t prim_bytes = ws_bytes - ivf_al(static_cast<size_t>(n) * 4);
+    rocprim::counting_iterator<int32_t> iota(0);
+    const unsigned bits = static_cast<unsigned>(ivf_key_bits(nlist));
+    size_t need = 0;
+    hipError_t e = rocprim::radix_sort_pairs(nullptr, need, list_of, sorted, iota, list_ids, static_cast<size_t>(n), 0u, bits, s);
+    if (e != hipSuccess) return static_cast<int>(e);
+    if (need > prim_bytes) return LR_EWORKSPACE;
+    e = rocprim::radix_sort_pairs(prim, need, list_of, sorted, iota, list_ids, static_cast<size_t>(n), 0u, bits, s);
+    if (e != hipSuccess) return static_cast<int>(e);
+    hipLaunchKernelGGL(ivf_list_ptr_kernel, dim3(grid_for(nlist + 1, kBlock)), dim3(kBlock), 0, s, sorted, n, nlist, list_ptr);
+  } else {
+    hipLaunchKernelGGL(ivf_list_ptr_kernel, dim3(grid_for(nlist + 1, kBlock)), dim3(kBlock), 0, s,
+                       static_cast<const int32_t*>(nullptr), int64_t(0), nlist, list_ptr);
+  }
+  return launch_status();
+}
+
+extern "C" size_t lr_ivf_centroids_ws_bytes(int64_t n, int D) {
+  if (n < 0 || D < 1) return 0;
+  return ivf_al(static_cast<size_t>(ceil_div(n, kIvfCH)) * 2 * D * sizeof(float)) + 256;
+}
+
+extern "C" int lr_ivf_centroids_f32(const float* rows, int64_t n_rows, int D, const int64_t* list_ptr, const int32_t* list_ids,
+                                    int64_t n, int nlist, float* centroids, void* ws, size_t ws_bytes, lr_stream_t stream) {
+  LR_CHECK_ARG(n >= 0 && n_rows >= 0 && nlist >= 1);
+  if (!ivf_row_shape_ok(D) || nlist > 65536 || n >= (int64_t(1) << 31)) return LR_ESHAPE;
+  if (n == 0) return LR_OK;
+  LR_CHECK_ARG(rows && list_ptr && list_ids && centroids && ws);
+  LR_CHECK_ARG(reinterpret_cast<uintptr_t>(rows) % 16 == 0 && reinterpret_cast<uintptr_t>(centroids) % 16 == 0 &&
+               reinterpret_cast<uintptr_t>(ws) % 16 == 0);
+  if (ws_bytes < lr_ivf_centroids_ws_bytes(n, D)) return LR_EWORKSPACE;
+  hipStream_t s = as_stream(stream);
+  float* part = static_cast<float*>(ws);
+  hipLaunchKernelGGL(ivf_centroid_chunk_kernel, dim3(grid_for(ceil_div(n, kIvfCH), kBlock / kWave)), dim3(kBlock), 0, s, rows, D,
+                     list_ptr, list_ids, n, nlist, n_rows, centroids, part);
+  hipLaunchKernelGGL(ivf_centroid_fold_kernel, dim3(grid_for(nlist, 1)), dim3(kBlock), 0, s, D, list_ptr, nlist, centroids, part);
+  return launch_status();
+}
+
+extern "C" int lr_ivf_search_f32(const float* queries, int64_t B, const float* centroids, int nlist, const int64_t* list_ptr,
+                                 const int32_t* list_ids, const float* list_rows, int64_t N, int D,
+                                 const int64_t* consumed_ptr, const int32_t* consumed_idx, const uint8_t* filter_flag, int k,
+                                 int nprobe, float* out_scores, int64_t* out_ids, void* ws, size_t ws_bytes,
+                                 lr_stream_t stream) {
+  LR_CHECK_ARG(B >= 0);
+  if (B == 0) return LR_OK;
+  const IvfPlan p = ivf_plan(B, N, D, k, nprobe, nlist);
+  if (!p.ok) return LR_ESHAPE;
+  LR_CHECK_ARG(queries && centroids && list_ptr && list_ids && list_rows && out_scores && out_ids);
+  LR_CHECK_ARG(reinterpret_cast<uintptr_t>(queries) % 16 == 0 && reinterpret_cast<uintptr_t>(centroids) % 16 == 0 &&
+               reinterpret_cast<uintptr_t>(list_rows) % 16 == 0);
+  if (ws == nullptr || ws_bytes < p.total) return LR_EWORKSPACE;
+  LR_CHECK_ARG(reinterpret_cast<uintptr_t>(ws) % 256 == 0);
+  hipStream_t s = as_stream(stream);
+  char* w = static_cast<char*>(ws);
+  float* cs = reinterpret_cast<float*>(w + p.off_cs);
+  int64_t* ci = reinterpret_cast<int64_t*>(w + p.off_ci);
+  int32_t* pref = reinterpret_cast<int32_t*>(w + p.off_pref);
+  int32_t* cnt = reinterpret_cast<int32_t*>(w + p.off_cnt);
+  uint64_t* keys = reinterpret_cast<uint64_t*>(w + p.off_keys);
+  int rc = lr_score_topk_f32(queries, B, centroids, nlist, D, nullptr, nullptr, nullptr, nprobe, 0, cs, ci, w + p.off_coarse,
+                             p.coarse_bytes, stream);
+  if (rc != LR_OK) return rc;
+  hipLaunchKernelGGL(ivf_plan_kernel, dim3(1), dim3(1024), 0, s, ci, p.P, list_ptr, nlist, p.CL, pref);
+  const size_t lds = static_cast<size_t>(4) * p.C * sizeof(uint64_t);
+  const dim3 grid(grid_for(p.Wmax, 4)), block(kBlock);
+  const int nch = D <= 64 ? 1 : D <= 128 ? 2 : 4;
+#define LR_IVF_SCAN(NCH)                                                                                                       \
+  hipLaunchKernelGGL(ivf_scan_kernel<NCH>, grid, block, lds, s, queries, D, ci, nprobe, p.P, pref, list_ptr, list_ids, list_rows, \
+                     consumed_ptr, consumed_idx, filter_flag, k, p.C, p.CL, p.Wmax, keys, cnt)
+  if (nch == 1) LR_IVF_SCAN(1);
+  else if (nch == 2) LR_IVF_SCAN(2);
+  else LR_IVF_SCAN(4);
+#undef LR_IVF_SCAN
+  hipLaunchKernelGGL(ivf_merge_kernel, dim3(static_cast<unsigned>(B)), block, lds + 64, s, pref, nprobe, keys, cnt, k, p.C, p.K2, p.Wmax,
+                     out_scores, out_ids);
+  return launch_status();
+}

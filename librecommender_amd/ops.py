@@ -1095,6 +1095,148 @@ def score_topk(users: torch.Tensor, items: torch.Tensor, k: int,
 
 
 # --------------------------------------------------------------------------------------
+# IVF-Flat index (csrc/ivf.hip): assignment, list build, centroid means, list scan with fused filter + top-k
+# --------------------------------------------------------------------------------------
+IVF_MAX_NLIST = 65536
+IVF_MAX_K = 1024
+
+
+def _ivf_pad(*mats: torch.Tensor):
+    """Rows of a width that is no multiple of 4 are zero-padded (16-byte rows), as `score_topk` does."""
+    D = mats[0].shape[1]
+    if D % 4 == 0:
+        return mats
+    pad = 4 - D % 4
+    return tuple(torch.nn.functional.pad(m, (0, pad)).contiguous() for m in mats)
+
+
+def _ivf_check_width(D: int, what: str) -> None:
+    if D < 1 or D > 256:
+        raise ValueError(f"{what}: shape not supported (row width {D} outside 1..256)")
+
+
+def ivf_assign(rows: torch.Tensor, centroids: torch.Tensor, want_score: bool = False):
+    """int32 [n]: for every row the centroid of largest inner product, ties to the lowest list id (`lr_ivf_assign_f32`);
+    with `want_score` also that inner product."""
+    if rows.dim() != 2 or centroids.dim() != 2 or rows.shape[1] != centroids.shape[1]:
+        raise ValueError("rows and centroids must be 2-d and share the embedding width")
+    n, D = rows.shape
+    nlist = centroids.shape[0]
+    if nlist < 1 or nlist > IVF_MAX_NLIST or n >= 2 ** 31:
+        raise ValueError(f"ivf_assign: shape not supported (n={n}, nlist={nlist})")
+    _ivf_check_width(D, "ivf_assign")
+    _req(rows, torch.float32, "rows", 2)
+    _req(centroids, torch.float32, "centroids", 2)
+    rows, centroids = _ivf_pad(rows, centroids)
+    out = torch.empty(n, dtype=torch.int32, device=rows.device)
+    best = torch.empty(n, dtype=torch.float32, device=rows.device) if want_score else None
+    _call("lr_ivf_assign_f32", _ptr(rows), n, _ptr(centroids), nlist, rows.shape[1], _ptr(out), _ptr(best), _stream())
+    return (out, best) if want_score else out
+
+
+def ivf_build_lists(list_of: torch.Tensor, nlist: int, rows: Optional[torch.Tensor] = None):
+    """Stable counting sort of the assignment: `list_ptr` int64 [nlist + 1], `list_ids` int32 [n] ascending within a list and,
+    when `rows` is given, `list_rows` = rows[list_ids] (`lr_ivf_build_lists` + `lr_embed_gather_f32`)."""
+    if not 1 <= int(nlist) <= IVF_MAX_NLIST:
+        raise ValueError(f"ivf_build_lists: shape not supported (nlist={nlist})")
+    _req(list_of, torch.int32, "list_of", 1)
+    n = list_of.numel()
+    if rows is not None:
+        _req(rows, torch.float32, "rows", 2)
+        if rows.shape[0] != n:
+            raise ValueError("rows and list_of must have one entry per row")
+    dev = list_of.device
+    list_ptr = torch.empty(nlist + 1, dtype=torch.int64, device=dev)
+    list_ids = torch.empty(n, dtype=torch.int32, device=dev)
+    ws = torch.empty(max(_lib.load().lr_ivf_build_ws_bytes(n, nlist), 256), dtype=torch.uint8, device=dev)
+    _call("lr_ivf_build_lists", _ptr(list_of), n, int(nlist), _ptr(list_ptr), _ptr(list_ids), _ptr(ws), ws.numel(), _stream())
+    if rows is None:
+        return list_ptr, list_ids
+    list_rows = embed_gather(rows, list_ids) if n else torch.empty((0, rows.shape[1]), dtype=torch.float32, device=dev)
+    return list_ptr, list_ids, list_rows
+
+
+def ivf_centroids(rows: torch.Tensor, list_ptr: torch.Tensor, list_ids: torch.Tensor, centroids: torch.Tensor) -> torch.Tensor:
+    """In place: `centroids[l]` = f32 mean of `rows[list_ids[list_ptr[l]:list_ptr[l+1]]]` (fixed summation order, one division);
+    an empty list keeps its centroid (`lr_ivf_centroids_f32`).  Widths that are no multiple of 4 are not taken here."""
+    _req(rows, torch.float32, "rows", 2)
+    _req(centroids, torch.float32, "centroids", 2)
+    _req(list_ptr, torch.int64, "list_ptr", 1)
+    _req(list_ids, torch.int32, "list_ids", 1)
+    D = rows.shape[1]
+    nlist = centroids.shape[0]
+    if centroids.shape[1] != D or list_ptr.numel() != nlist + 1:
+        raise ValueError("centroids must be [nlist, D] and list_ptr [nlist + 1]")
+    if D % 4 != 0 or D > 256 or nlist > IVF_MAX_NLIST:
+        raise ValueError(f"ivf_centroids: shape not supported (D={D}, nlist={nlist})")
+    n = list_ids.numel()
+    ws = torch.empty(max(_lib.load().lr_ivf_centroids_ws_bytes(n, D), 256), dtype=torch.uint8, device=rows.device)
+    _call("lr_ivf_centroids_f32", _ptr(rows), rows.shape[0], D, _ptr(list_ptr), _ptr(list_ids), n, nlist, _ptr(centroids),
+          _ptr(ws), ws.numel(), _stream())
+    return centroids
+
+
+def ivf_check_search_args(B: int, N: int, D: int, Dq: int, k: int, nprobe: int, nlist: int) -> None:
+    """The argument errors of `ivf_search`, raised before a device is needed."""
+    if D != Dq:
+        raise ValueError(f"queries have width {Dq}, the index {D}")
+    if k < 1:
+        raise ValueError(f"k must be >= 1, got {k}")
+    if nlist > N:
+        raise ValueError(f"nlist {nlist} exceeds the number of rows {N}")
+    if nprobe < 1 or nprobe > nlist:
+        raise ValueError(f"nprobe must be in 1..nlist ({nlist}), got {nprobe}")
+
+
+def ivf_search(queries: torch.Tensor, centroids: torch.Tensor, list_ptr: torch.Tensor, list_ids: torch.Tensor,
+               list_rows: torch.Tensor, k: int, nprobe: int, consumed_ptr: Optional[torch.Tensor] = None,
+               consumed_idx: Optional[torch.Tensor] = None, filter_flag: Optional[torch.Tensor] = None,
+               out: Optional[tuple] = None):
+    """Top-k by (score desc, global id asc) among the rows of the `nprobe` best lists of every query (`lr_ivf_search_f32`);
+    the output contract is `score_topk`'s.  `out`: (scores [B, k] f32, ids [B, k] int64) to write into."""
+    if queries.dim() != 2 or centroids.dim() != 2 or list_rows.dim() != 2:
+        raise ValueError("queries, centroids and list_rows must be 2-d")
+    B, Dq = queries.shape
+    N, D = list_rows.shape
+    nlist = centroids.shape[0]
+    k, nprobe = int(k), int(nprobe)
+    ivf_check_search_args(B, N, D, Dq, k, nprobe, nlist)
+    if centroids.shape[1] != D or list_ptr.numel() != nlist + 1 or list_ids.numel() != N:
+        raise ValueError("centroids / list_ptr / list_ids do not describe list_rows")
+    _ivf_check_width(D, "ivf_search")
+    Dp = (D + 3) // 4 * 4
+    lib = _lib.load()
+    if B > 0 and not lib.lr_ivf_supported(B, N, Dp, k, nprobe, nlist):
+        raise ValueError(f"ivf_search: shape not supported (B={B} N={N} D={D} k={k} nprobe={nprobe} nlist={nlist})")
+    _req(queries, torch.float32, "queries", 2)
+    _req(centroids, torch.float32, "centroids", 2)
+    _req(list_rows, torch.float32, "list_rows", 2)
+    _req(list_ptr, torch.int64, "list_ptr", 1)
+    _req(list_ids, torch.int32, "list_ids", 1)
+    if consumed_ptr is not None:
+        _req(consumed_ptr, torch.int64, "consumed_ptr", 1)
+        _req(consumed_idx, torch.int32, "consumed_idx", 1)
+    if filter_flag is not None:
+        _req(filter_flag, torch.uint8, "filter_flag", 1)
+    queries, centroids, list_rows = _ivf_pad(queries, centroids, list_rows)
+    dev = queries.device
+    if out is None:
+        out_s = torch.empty((B, k), dtype=torch.float32, device=dev)
+        out_i = torch.empty((B, k), dtype=torch.int64, device=dev)
+    else:
+        out_s, out_i = _req(out[0], torch.float32, "out scores", 2), _req(out[1], torch.int64, "out ids", 2)
+        if tuple(out_s.shape) != (B, k) or tuple(out_i.shape) != (B, k):
+            raise ValueError("out must be ([B, k] f32, [B, k] int64)")
+    if B == 0:
+        return out_s, out_i
+    ws = torch.empty(lib.lr_ivf_search_ws_bytes(B, N, Dp, k, nprobe, nlist), dtype=torch.uint8, device=dev)
+    _call("lr_ivf_search_f32", _ptr(queries), B, _ptr(centroids), nlist, _ptr(list_ptr), _ptr(list_ids), _ptr(list_rows), N, Dp,
+          _ptr(consumed_ptr), _ptr(consumed_idx), _ptr(filter_flag), k, nprobe, _ptr(out_s), _ptr(out_i), _ptr(ws), ws.numel(),
+          _stream())
+    return out_s, out_i
+
+
+# --------------------------------------------------------------------------------------
 # streaming in-batch softmax cross-entropy (two-tower retrieval loss)
 # --------------------------------------------------------------------------------------
 # Arithmetic of the two contractions of the streaming softmax cross-entropy: "split_bf16" (default) forms every f32 product as

@@ -3,7 +3,13 @@
 The reference's embed serving (`libserving/sanic_serving/embed_deploy.py:21-62`) answers `/embed/recommend` by a
 faiss inner-product search over the item vectors for `n_rec + len(consumed)` candidates and drops the user's consumed
 items.  Here the request handler's compute is one exact `lr_score_topk_f32` launch per batch of users with the
-consumed lists filtered inside the kernel; the HTTP / Redis plumbing around it is out of scope."""
+consumed lists filtered inside the kernel; the HTTP / Redis plumbing around it is out of scope.
+
+With `use_index=True` (the default) and an `ivf_index.npz` in the directory (`serving.save_ivf_index`, the counterpart of the reference's
+`faiss_index.bin`) `recommend` goes through the IVF-Flat index instead (`lr_ivf_search_f32`): the probed lists are
+scanned with the consumed ids filtered inside the kernel, which equals the reference's "search n_rec + len(consumed), drop
+consumed, take n_rec" whenever the probed lists hold that many rows (where they hold fewer, the reference answers with fewer
+than n_rec items and this search still returns what the lists hold)."""
 from __future__ import annotations
 
 import json
@@ -21,7 +27,7 @@ class InvalidUser(KeyError):
 
 
 class EmbedServer:
-    def __init__(self, path: str, device="cuda"):
+    def __init__(self, path: str, device="cuda", use_index: bool = True):
         def load(name):
             with open(os.path.join(path, name)) as f:
                 return json.load(f)
@@ -41,6 +47,10 @@ class EmbedServer:
         self._ptr = consumed.ptr                                       # CSR of ascending unique ids (the kernel's contract)
         self._consumed = torch.from_numpy(consumed.items).to(self.device)
         self._item_raw = np.array([self.id2item[str(i)] for i in range(self.n_items)])
+        self.index = None
+        if use_index and os.path.exists(os.path.join(path, "ivf_index.npz")):
+            from ..recommendation.ivf import IVFFlatIndex
+            self.index = IVFFlatIndex.load(path, self.device, self.item_embeds)
 
     def recommend(self, users: Sequence, n_rec: int) -> Dict[object, List]:
         """{raw user: [raw item ids]}: the `n_rec` highest inner products among the items the user has not consumed
@@ -58,8 +68,12 @@ class EmbedServer:
         cidx = self._consumed[torch.from_numpy(take).to(self.device)] if len(take) else self._consumed[:0]
         dev = self.device
         U = self.user_embeds.index_select(0, torch.from_numpy(uid).to(dev)).contiguous()
-        scores, ids = ops.score_topk(U, self.item_embeds, k, torch.from_numpy(ptr.astype(np.int64)).to(dev),
-                                     cidx.to(torch.int32).contiguous(), torch.ones(len(uid), dtype=torch.uint8, device=dev))
+        cptr, cidx = torch.from_numpy(ptr.astype(np.int64)).to(dev), cidx.to(torch.int32).contiguous()
+        flag = torch.ones(len(uid), dtype=torch.uint8, device=dev)
+        if self.index is not None:
+            scores, ids = self.index.search(U, k, None, cptr, cidx, flag)
+        else:
+            scores, ids = ops.score_topk(U, self.item_embeds, k, cptr, cidx, flag)
         ids, scores = ids.cpu().numpy(), scores.cpu().numpy()
         out = {}
         for j, u in enumerate(users):

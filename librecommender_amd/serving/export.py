@@ -115,3 +115,24 @@ def save_knn(path: str, model, k: int):
     ids, sims, lens = (t.cpu().numpy() for t in ops.cf_topk(sim.ptr, sim.col, sim.val, k))
     _dump(path, "sim.json", {str(i): [[int(a), float(b)] for a, b in zip(ids[i, :n].tolist(), sims[i, :n].tolist())]
                              for i, n in enumerate(lens.tolist())})
+
+
+def save_ivf_index(path: str, model, nlist: int = 80, nprobe: int = 10):
+    """The reference's `save_faiss_index` (`embed.py:42-54`: `IndexIVFFlat(IndexFlatIP, d, nlist, METRIC_INNER_PRODUCT)`, trained
+    on and filled with `model.item_embeds[: n_items]`), as this library's own index (`recommendation/ivf.py`):
+    `<path>/ivf_index.npz` holds centroids, list_ptr, list_ids, nprobe and d.  faiss's binary format is not written."""
+    import torch
+
+    from ..recommendation.ivf import IVFFlatIndex, check_train_args
+
+    _ensure_dir(path)
+    items = model.item_embeds
+    if items is not None and not isinstance(items, torch.Tensor):
+        items = items.gather()                    # sharded export: assembled on request
+    assert items is not None, "call `model.fit()` before saving the index"
+    items = items[: model.n_items]
+    check_train_args(items.shape[0], items.shape[1], int(nlist), 20)
+    if not 1 <= int(nprobe) <= int(nlist):
+        raise ValueError(f"nprobe must be in 1..nlist ({nlist}), got {nprobe}")
+    index = IVFFlatIndex.train_add(items.to(torch.float32).contiguous(), nlist, nprobe=nprobe)
+    return index.save(path)

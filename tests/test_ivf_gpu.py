@@ -1,0 +1,337 @@
+"""The IVF-Flat kernels (csrc/ivf.hip), `IVFFlatIndex` and its three seams against the numpy oracle (tests/ivf_oracle.py).
+
+Kernel-level inputs lie on a grid (multiples of 1/4 in [-2, 2]): every product and every partial sum of up to 256 of them is
+exact in f32, so scores and sums must equal the oracle's BIT FOR BIT in any summation order, and ties are plentiful, which is
+what exercises the tie rules (lowest list id, lowest global id)."""
+import os
+
+import numpy as np
+import pandas as pd
+import pytest
+import torch
+
+from librecommender_amd import _lib, ops
+from librecommender_amd.recommendation.ivf import IVFFlatIndex
+
+from . import ivf_oracle as O
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(__file__)
+DATA = os.path.join(HERE, "golden", "sample_movielens_rating.dat")
+
+
+def _dev(a, dev):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+
+def _assignment(rng, rows, cent, kind):
+    """list id per row: the oracle's assignment ("assign"), uniform with lists 1 and nlist - 1 left empty ("empty"), or about
+    90 % of the rows in one list ("skew")."""
+    n, nlist = rows.shape[0], cent.shape[0]
+    if kind == "assign":
+        return O.assign(rows, cent)
+    a = rng.integers(0, nlist, size=n).astype(np.int32)
+    if kind == "empty" and nlist > 2:
+        a[(a == 1) | (a == nlist - 1)] = 0
+    if kind == "skew":
+        a[rng.random(n) < 0.9] = nlist // 2
+    return a
+
+
+# ---- assignment -------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("D", [4, 6, 16, 20, 128, 256])
+@pytest.mark.parametrize("n,nlist", [(1, 1), (63, 2), (64, 7), (65, 64), (1000, 80), (5000, 7)])
+def test_assign(dev, D, n, nlist):
+    rng = np.random.default_rng(1000 * D + n)
+    rows, cent = O.grid(rng, (n, D)), O.grid(rng, (nlist, D))
+    cent[nlist // 2] = cent[0]                                     # an exact duplicate: the lower id must win
+    exp, s = O.assign(rows, cent, want_scores=True)
+    got, best = ops.ivf_assign(_dev(rows, dev), _dev(cent, dev), want_score=True)
+    assert np.array_equal(got.cpu().numpy(), exp)
+    assert np.array_equal(best.cpu().numpy(), s.max(axis=1).astype(np.float32))
+    assert np.array_equal(ops.ivf_assign(_dev(rows, dev), _dev(cent, dev)).cpu().numpy(), exp)
+
+
+# ---- list build -------------------------------------------------------------------------------------------------------
+LIST_CASES = [(1, 1, "uniform"), (63, 2, "uniform"), (65, 7, "empty"), (1000, 80, "empty"), (5000, 64, "skew"), (5000, 7, "skew"),
+              (64, 64, "uniform")]
+
+
+@pytest.mark.parametrize("D", [4, 20])
+@pytest.mark.parametrize("n,nlist,kind", LIST_CASES)
+def test_build_lists(dev, D, n, nlist, kind):
+    rng = np.random.default_rng(7 * n + nlist)
+    rows = O.grid(rng, (n, D))
+    a = _assignment(rng, rows, np.zeros((nlist, D), np.float32), kind)
+    ptr, ids = O.build_lists(a, nlist)
+    if kind == "empty" and nlist > 2:
+        assert ptr[1] == ptr[2] and ptr[nlist - 1] == ptr[nlist]
+    if kind == "skew":
+        assert (ptr[nlist // 2 + 1] - ptr[nlist // 2]) > 0.85 * n
+    g_ptr, g_ids, g_rows = ops.ivf_build_lists(_dev(a, dev), nlist, _dev(rows, dev))
+    assert g_ptr.dtype == torch.int64 and g_ids.dtype == torch.int32
+    assert np.array_equal(g_ptr.cpu().numpy(), ptr)
+    assert np.array_equal(g_ids.cpu().numpy(), ids)
+    assert np.array_equal(g_rows.cpu().numpy(), rows[ids])
+    p2, i2 = ops.ivf_build_lists(_dev(a, dev), nlist)
+    assert torch.equal(p2, g_ptr) and torch.equal(i2, g_ids)
+
+
+# ---- centroid means ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("D", [4, 20, 128, 256])
+@pytest.mark.parametrize("n,nlist,kind", [(1, 1, "uniform"), (65, 7, "empty"), (1000, 80, "uniform"), (5000, 7, "skew"),
+                                          (5000, 64, "empty"), (2048, 2, "uniform")])
+def test_centroids(dev, D, n, nlist, kind):
+    """Bit-equal to np.float32(sum) / np.float32(count): the sums are exact on the grid (|sum| <= 2 * 5000, multiples of 1/4)
+    and the one division is correctly rounded on both sides; empty lists keep their row."""
+    rng = np.random.default_rng(13 * n + D)
+    rows, prev = O.grid(rng, (n, D)), O.grid(rng, (nlist, D))
+    ptr, ids = O.build_lists(_assignment(rng, rows, prev, kind), nlist)
+    exp = O.centroid_means(rows, ptr, ids, prev)
+    cent = _dev(prev, dev)
+    out = ops.ivf_centroids(_dev(rows, dev), _dev(ptr, dev), _dev(ids, dev), cent)
+    assert out is cent
+    assert np.array_equal(cent.cpu().numpy().view(np.uint32), exp.view(np.uint32))
+
+
+# ---- search -----------------------------------------------------------------------------------------------------------
+def _index(rng, N, nlist, D, kind):
+    rows, cent = O.grid(rng, (N, D)), O.grid(rng, (nlist, D))
+    ptr, ids = O.build_lists(_assignment(rng, rows, cent, kind), nlist)
+    return rows, cent, ptr, ids
+
+
+def _consumed(rng, B, N, frac=0.2):
+    """One ascending id array per query (some empty), the CSR of them and flags with every third query's filter off."""
+    lists = [np.sort(rng.choice(N, size=int(rng.integers(0, max(1, int(frac * N)) + 1)), replace=False)).astype(np.int32)
+             if q % 4 != 1 else np.zeros(0, np.int32) for q in range(B)]
+    flags = np.array([0 if q % 3 == 2 else 1 for q in range(B)], dtype=np.uint8)
+    return lists, flags
+
+
+def _csr(lists):
+    ptr = np.zeros(len(lists) + 1, dtype=np.int64)
+    ptr[1:] = np.cumsum([len(c) for c in lists])
+    return ptr, np.concatenate(lists + [np.zeros(0, np.int32)]).astype(np.int32)
+
+
+def _search(dev, rows, cent, ptr, ids, queries, k, nprobe, lists=None, flags=None, out=None):
+    args = [_dev(queries, dev), _dev(cent, dev), _dev(ptr, dev), _dev(ids, dev), _dev(rows[ids], dev), k, nprobe]
+    if lists is not None:
+        cp, ci = _csr(lists)
+        args += [_dev(cp, dev), _dev(ci, dev), None if flags is None else _dev(flags, dev)]
+    s, i = ops.ivf_search(*args, out=out) if out is not None else ops.ivf_search(*args)
+    return s.cpu().numpy(), i.cpu().numpy()
+
+
+def _same(got, exp):
+    (gs, gi), (es, ei) = got, exp
+    assert np.array_equal(gi, ei)
+    assert np.array_equal(gs.view(np.uint32), es.view(np.uint32))
+
+
+# (N, nlist, D, B, k, nprobe, kind)
+SEARCH_CASES = [
+    (1, 1, 4, 1, 1, 1, "assign"),
+    (1000, 7, 16, 3, 10, 1, "assign"),
+    (1000, 7, 16, 3, 10, 3, "assign"),
+    (63, 2, 4, 1, 100, 2, "assign"),            # k above the number of rows: -1 / -inf fill
+    (64, 64, 20, 64, 10, 5, "uniform"),
+    (65, 64, 256, 257, 1, 5, "assign"),
+    (5000, 80, 128, 65, 100, 80, "assign"),     # every list probed
+    (5000, 80, 128, 3, 100, 9, "empty"),
+    (5000, 64, 20, 64, 100, 8, "skew"),         # one list holds about 90 % of the rows
+    (5000, 7, 128, 1, 100, 7, "skew"),
+    (1000, 80, 6, 3, 1024, 80, "assign"),       # nprobe * k = 81,920 > 8,192 and k > N, through the host pad
+    (5000, 80, 128, 1, 1024, 10, "assign"),     # nprobe * k = 10,240 > 8,192
+]
+
+
+@pytest.mark.parametrize("N,nlist,D,B,k,nprobe,kind", SEARCH_CASES)
+def test_search(dev, N, nlist, D, B, k, nprobe, kind):
+    rng = np.random.default_rng(N + 31 * nlist + D + B + k + nprobe)
+    rows, cent, ptr, ids = _index(rng, N, nlist, D, kind)
+    queries = O.grid(rng, (B, D))
+    _same(_search(dev, rows, cent, ptr, ids, queries, k, nprobe), O.search(queries, cent, ptr, ids, rows, k, nprobe))
+    lists, flags = _consumed(rng, B, N)
+    _same(_search(dev, rows, cent, ptr, ids, queries, k, nprobe, lists, flags),
+          O.search(queries, cent, ptr, ids, rows, k, nprobe, lists, flags))
+    _same(_search(dev, rows, cent, ptr, ids, queries, k, nprobe, lists, None),
+          O.search(queries, cent, ptr, ids, rows, k, nprobe, lists, None))
+
+
+@pytest.mark.parametrize("nprobe", [1, 2])
+def test_search_consumed_list_empties_a_probed_list(dev, nprobe):
+    rng = np.random.default_rng(5)
+    N, nlist, D, k = 1000, 7, 16, 10
+    rows, cent, ptr, ids = _index(rng, N, nlist, D, "assign")
+    queries = O.grid(rng, (3, D))
+    best = O.rank(O.scores64(queries, cent)[0], np.arange(nlist))[0]
+    assert ptr[best + 1] > ptr[best]
+    lists = [np.sort(ids[ptr[best]:ptr[best + 1]]).astype(np.int32), np.zeros(0, np.int32), np.arange(N, dtype=np.int32)]
+    got = _search(dev, rows, cent, ptr, ids, queries, k, nprobe, lists, None)
+    _same(got, O.search(queries, cent, ptr, ids, rows, k, nprobe, lists, None))
+    if nprobe == 1:
+        assert (got[1][0] == -1).all() and np.isneginf(got[0][0]).all()
+    assert (got[1][2] == -1).all()                                  # everything consumed
+
+
+@pytest.mark.parametrize("N,nlist,D,B,k", [(5000, 80, 128, 65, 100), (1000, 7, 20, 3, 10), (1000, 80, 6, 3, 10)])
+def test_full_probe_equals_the_exact_scan(dev, N, nlist, D, B, k):
+    rng = np.random.default_rng(N + D)
+    rows, cent, ptr, ids = _index(rng, N, nlist, D, "assign")
+    queries = O.grid(rng, (B, D))
+    lists, flags = _consumed(rng, B, N)
+    cp, ci = _csr(lists)
+    es, ei = ops.score_topk(_dev(queries, dev), _dev(rows, dev), k, _dev(cp, dev), _dev(ci, dev), _dev(flags, dev), arith="f32_chain")
+    _same(_search(dev, rows, cent, ptr, ids, queries, k, nlist, lists, flags), (es.cpu().numpy(), ei.cpu().numpy()))
+
+
+def test_two_runs_give_the_same_bits(dev):
+    rng = np.random.default_rng(11)
+    N, nlist, D = 5000, 64, 128
+    rows = (rng.standard_normal((N, D)) * 0.3).astype(np.float32)       # off the grid: rounding takes part
+    queries = rng.standard_normal((65, D)).astype(np.float32)
+    runs = []
+    for _ in range(2):
+        idx = IVFFlatIndex.train_add(_dev(rows, dev), nlist, niter=3)
+        s, i = idx.search(_dev(queries, dev), 100, nprobe=8)
+        runs.append((idx.centroids.clone(), idx.list_ptr.clone(), idx.list_ids.clone(), idx.list_rows.clone(), s, i))
+    for a, b in zip(*runs):
+        assert torch.equal(a, b)
+
+
+def test_unsupported_shapes_raise_and_write_nothing(dev):
+    rng = np.random.default_rng(3)
+    N, nlist, D, B = 1000, 7, 16, 3
+    rows, cent, ptr, ids = _index(rng, N, nlist, D, "assign")
+    queries = O.grid(rng, (B, D))
+    for k, D_bad in ((1025, None), (10, 6), (10, 260)):
+        out_s = torch.full((B, k), 1234.5, dtype=torch.float32, device=dev)
+        out_i = torch.full((B, k), 777, dtype=torch.int64, device=dev)
+        if D_bad is None:
+            with pytest.raises(ValueError, match="shape not supported"):
+                _search(dev, rows, cent, ptr, ids, queries, k, 2, out=(out_s, out_i))
+        else:                                    # the C entry point itself: a width it does not take (the wrapper would pad 6)
+            t = [_dev(x, dev) for x in (queries, cent, ptr, ids, rows[ids])]
+            ws = torch.zeros(1 << 20, dtype=torch.uint8, device=dev)
+            with pytest.raises(ValueError):
+                ops._call("lr_ivf_search_f32", t[0].data_ptr(), B, t[1].data_ptr(), nlist, t[2].data_ptr(), t[3].data_ptr(),
+                          t[4].data_ptr(), N, D_bad, 0, 0, 0, k, 2, out_s.data_ptr(), out_i.data_ptr(), ws.data_ptr(), ws.numel(),
+                          ops._stream())
+            assert _lib.load().lr_ivf_supported(B, N, D_bad, k, 2, nlist) == 0
+        torch.cuda.synchronize()
+        assert (out_s == 1234.5).all() and (out_i == 777).all()
+    with pytest.raises(ValueError, match="shape not supported"):
+        ops.ivf_assign(torch.zeros((4, 260), device=dev), torch.zeros((2, 260), device=dev))
+    with pytest.raises(ValueError, match="shape not supported"):
+        ops.ivf_build_lists(torch.zeros(4, dtype=torch.int32, device=dev), 65537)
+    with pytest.raises(ValueError, match="shape not supported"):
+        ops.ivf_centroids(torch.zeros((4, 6), device=dev), torch.zeros(3, dtype=torch.int64, device=dev),
+                          torch.zeros(4, dtype=torch.int32, device=dev), torch.zeros((2, 6), device=dev))
+
+
+# ---- whole training ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("N,nlist,D", [(2000, 8, 16), (1100, 4, 20), (1500, 6, 6)])
+def test_training_on_a_separated_mixture(dev, N, nlist, D):
+    """Centres 10 e_i (orthogonal directions), noise of scale 0.1; row i belongs to centre floor(i nlist / N), so the
+    deterministic init draws one row per centre ((1100, 4): 1,024 of the rows train).  Well-posedness is asserted first, in fp64
+    on the oracle's own trajectory: every training row's gap between its best and second-best centroid score exceeds 1e-3 of the
+    score scale in every round.  Then the lists must equal the oracle's exactly, and a centroid element may differ from the
+    oracle's (fp64 sum, rounded once) by count * 2^-23 * max|row element|: an f32 sum of `count` terms of that scale errs by at
+    most count * 2^-24 * sum|x| <= count^2 * 2^-24 * max|x| before the division by count, and the oracle's own rounding and the
+    division take the other factor of two."""
+    rng = np.random.default_rng(N)
+    centre = (np.arange(N) * nlist) // N
+    rows = (0.1 * rng.standard_normal((N, D))).astype(np.float32)
+    rows[np.arange(N), centre] += 10.0
+    cent, gap = O.train(rows, nlist, 20, want_gaps=True)
+    assert gap > 1e-3, f"ill-posed input: smallest relative gap {gap}"
+    list_of = O.assign(rows, cent)
+    assert np.array_equal(list_of, centre)                                  # the mixture was recovered
+    ptr, ids = O.build_lists(list_of, nlist)
+    idx = IVFFlatIndex.train_add(_dev(rows, dev), nlist)
+    assert np.array_equal(idx.list_ptr.cpu().numpy(), ptr) and np.array_equal(idx.list_ids.cpu().numpy(), ids)
+    assert np.array_equal(idx.list_rows.cpu().numpy()[:, :D], rows[ids])
+    got = idx.centroids.cpu().numpy()[:, :D]
+    n_train = min(N, 256 * nlist)
+    count = np.bincount(O.assign(rows[O.train_ids(N, nlist)], cent), minlength=nlist).astype(np.float64)
+    assert count.sum() == n_train
+    err = np.abs(got.astype(np.float64) - cent.astype(np.float64)).max(axis=1)
+    assert (err <= count * 2.0 ** -23 * np.abs(rows).max()).all(), (err, count)
+
+
+# ---- model level ------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def model(dev):
+    from librecommender_amd.algorithms import BPR
+    from librecommender_amd.data import DatasetPure
+
+    df = pd.read_csv(DATA, sep="::", engine="python", names=["user", "item", "label", "time"]).iloc[:20000]
+    train_data, info = DatasetPure.build_trainset(df)
+    m = BPR("ranking", info, embed_size=16, n_epochs=2, seed=7, use_tf=True)
+    m.fit(train_data, neg_sampling=True, verbose=0)
+    return m, info
+
+
+def test_init_knn_with_every_list_probed_is_the_exact_search(model):
+    m, info = model
+    users, items = list(info.user2id)[:8], list(info.item2id)[:8]
+    m.init_knn(False, "cosine")
+    exact = [m.search_knn_users(u, 10) for u in users] + [m.search_knn_items(i, 10) for i in items]
+    m.init_knn(False, "cosine", nlist=8, nprobe=8)
+    assert set(m._knn_index) == {"user", "item"}
+    assert [m.search_knn_users(u, 10) for u in users] + [m.search_knn_items(i, 10) for i in items] == exact
+    m.init_knn(True, "inner-product")
+    assert m._knn_index == {}
+
+
+def test_init_knn_nprobe_2_gives_the_oracles_neighbours(model):
+    m, info = model
+    m.init_knn(False, "cosine", nlist=8, nprobe=2)
+    for side, names, fn in (("user", list(info.user2id)[:8], m.search_knn_users), ("item", list(info.item2id)[:8], m.search_knn_items)):
+        idx, rows = m._knn_index[side], m._knn_rows[side].cpu().numpy()
+        assert idx.nprobe == 2
+        cent, ptr, ids = idx.centroids.cpu().numpy(), idx.list_ptr.cpu().numpy(), idx.list_ids.cpu().numpy()
+        id2name = info.id2user if side == "user" else info.id2item
+        name2id = info.user2id if side == "user" else info.item2id
+        for name in names:
+            q = rows[name2id[name]][None]
+            _, ei = O.search(q, cent, ptr, ids, rows, 10, 2)
+            assert fn(name, 10) == [id2name[int(i)] for i in ei[0] if i >= 0]
+
+
+def test_embed_server_through_the_index(model, tmp_path):
+    from librecommender_amd import serving
+
+    m, info = model
+    path = str(tmp_path / "serve")
+    serving.save_embed(path, m)
+    exact = serving.EmbedServer(path, "cuda")                      # no index file yet: nothing changes
+    assert exact.index is None
+    file = serving.save_ivf_index(path, m, nlist=8, nprobe=8)
+    assert os.path.basename(file) == "ivf_index.npz" and sorted(np.load(file).files) == ["centroids", "d", "list_ids", "list_ptr", "nprobe"]
+    exact = serving.EmbedServer(path, "cuda", use_index=False)
+    served = serving.EmbedServer(path, "cuda", use_index=True)
+    assert exact.index is None and served.index is not None and served.index.nprobe == 8
+    users = list(info.user2id)[:50]
+    assert served.recommend(users, 10) == exact.recommend(users, 10)
+    for nprobe in (1, 2, 8):
+        served.index.nprobe = nprobe
+        for u, recs in served.recommend(users, 10).items():
+            seen = {info.id2item[i] for i in info.user_consumed[info.user2id[u]]}
+            assert len(recs) == len(set(recs)) and not seen & set(recs)
+
+
+def test_index_save_load_round_trip(model, dev, tmp_path):
+    m, _ = model
+    rows = m.item_embeds[: m.n_items].contiguous()
+    idx = IVFFlatIndex.train_add(rows, 8, nprobe=3)
+    idx.save(str(tmp_path))
+    back = IVFFlatIndex.load(str(tmp_path), dev, rows)
+    assert back.nprobe == 3 and back.d == idx.d and back.nlist == 8
+    q = m.user_embeds[:33].contiguous()
+    for a, b in zip(idx.search(q, 20), back.search(q, 20)):
+        assert torch.equal(a, b)
+    assert torch.equal(idx.list_rows, back.list_rows)
