@@ -1502,6 +1502,45 @@ int lr_ivf_search_f32(const float* queries, int64_t B, const float* centroids, i
                       const int32_t* consumed_idx, const uint8_t* filter_flag, int k, int nprobe, float* out_scores,
                       int64_t* out_ids, void* ws, size_t ws_bytes, lr_stream_t stream);
 
+/* ---- Evaluation metrics (csrc/eval_metrics.hip) — replaces the sklearn / numpy / Python-set work of
+ * libreco/evaluation/metrics.py (roc_gauc, precision_at_k, recall_at_k, average_precision_at_k, ndcg_at_k, coverage) and
+ * libreco/evaluation/evaluate.py:62-193 (roc_auc_score, precision_recall_curve + auc, log_loss, balanced_accuracy_score,
+ * r2_score, rmse, mae).  Fewer than 2^31 rows (LR_ESHAPE otherwise, nothing written).  No floating-point atomics: two calls give
+ * the same bits.  Every output element is written by every call; workspaces may hold anything.
+ *
+ * lr_eval_keys_f32: key[i] = (group[i] << 32) | image(score[i]), group 0 when `group` is NULL (groups are >= 0).  image is the
+ *   order-preserving unsigned 32-bit image of the float: -0.0 is +0.0 first, subnormals are not flushed.  bad[0] = the number of
+ *   NaN scores.  Sorting the keys ascending (the caller's job, carrying the labels) orders rows by (group, score).
+ * lr_eval_rank_stats: one segmented scan over tie runs (equal key) and groups (equal high word) of the SORTED keys; label != 0
+ *   is a positive.  out_i64 = {num2, P, Nneg}: num2 = sum over runs of pos_run * (2 * neg_below + neg_run), neg_below counted
+ *   within the run's group (with one group: ROC AUC = num2 / (2 P Nneg), exactly the tie-corrected rank statistic);
+ *   out_f64 = {gauc, pr_auc}: gauc = (sum over groups with both classes of n_g * num2_g / (2 P_g N_g)) / n (metrics.py roc_gauc;
+ *   a single-class group adds 0); pr_auc = the trapezoid area under sklearn's precision_recall_curve (thresholds = the distinct
+ *   keys, the last point recall 0 / precision 1), which reads the rows as one sequence and means something for one group only.
+ *   fp64 throughout, fixed summation order.  Workspace: lr_eval_rank_ws_bytes (0 outside the envelope), 256-byte aligned.
+ * lr_eval_point_sums_f32: out_f64 = {sum (y - p)^2, sum |y - p|, sum y, sum (y - mean)^2, log-loss sum}, differences and sums in
+ *   fp64; the log-loss term of a row is -log(clip(p)) for y != 0 and -log(clip(float32(1 - p))) otherwise, clip to
+ *   [2^-23, 1 - 2^-23] (sklearn's log_loss on float32 input).  out_i64 = {TP, TN, P, N} for labels in {0, 1} and the class
+ *   rint(p) (half to even: 0.5 is class 0).  Workspace: lr_eval_point_ws_bytes.
+ * lr_eval_listwise: reco int32 [U, k] (-1 padded, distinct ids), truth_items ascending and distinct within a user's
+ *   truth_ptr range, truth_len[u] >= 1 the divisor of recall, disc f64 [k] = 1 / log2(j + 2).  out f64 [4, U] = precision
+ *   (hits / k), recall (hits / truth_len), AP (mean of cumhits_j / (j + 1) over hit positions, 0 without hits) and NDCG
+ *   (sum hit_j disc_j / sum_{j < hits} disc_j, 0 without hits).  1 <= k <= 1024 (LR_ESHAPE otherwise).
+ * lr_eval_coverage_i32: flags int32 [n_items] = 1 where an id of reco[0 .. n) in [0, n_items) occurs, else 0; count[0] = the
+ *   number of set flags. */
+size_t lr_eval_rank_ws_bytes(int64_t n);
+size_t lr_eval_point_ws_bytes(int64_t n);
+int lr_eval_keys_f32(const float* score, const int32_t* group /* [n] or NULL */, int64_t n, int64_t* key, int32_t* bad /* [1] */,
+                     lr_stream_t stream);
+int lr_eval_rank_stats(const int64_t* key_sorted, const uint8_t* label_sorted, int64_t n, int64_t* out_i64 /* [3] */,
+                       double* out_f64 /* [2] */, void* ws, size_t ws_bytes, lr_stream_t stream);
+int lr_eval_point_sums_f32(const float* pred, const float* label, int64_t n, double mean, double* out_f64 /* [5] */,
+                           int64_t* out_i64 /* [4] */, void* ws, size_t ws_bytes, lr_stream_t stream);
+int lr_eval_listwise(const int32_t* reco, const int64_t* truth_ptr, const int32_t* truth_items, const int32_t* truth_len,
+                     const double* disc, int64_t U, int k, double* out /* [4, U] */, lr_stream_t stream);
+int lr_eval_coverage_i32(const int32_t* reco, int64_t n, int64_t n_items, int32_t* flags /* [n_items] */,
+                         int64_t* count /* [1] */, lr_stream_t stream);
+
 /* Measurement probe (scripts/mfma_peak.py): iters x 8 back-to-back v_mfma_f32_32x32x2_f32 per wave on
  * 256 x waves_per_simd workgroups — the f32 MFMA rate the chip sustains at the clock it holds under that load. */
 int lr_mfma_f32_probe(int iters, int waves_per_simd, float* out, lr_stream_t stream);

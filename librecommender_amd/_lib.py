@@ -307,6 +307,13 @@ SIGNATURES = {
     "lr_ncf_pair_bwd_f32": (_int, [_p, _p, _p, _p, _i64, _int, _p]),
     "lr_ncf_score_supported": (_int, [_int, _int, _p]),
     "lr_ncf_score_f32": (_int, [_p, _i64, _int, _p, _p, _i64, _int, _p, _p, _p, _p, _p, _p, _p, _f32, _p, _p]),
+    "lr_eval_rank_ws_bytes": (_sz, [_i64]),
+    "lr_eval_point_ws_bytes": (_sz, [_i64]),
+    "lr_eval_keys_f32": (_int, [_p, _p, _i64, _p, _p, _p]),
+    "lr_eval_rank_stats": (_int, [_p, _p, _i64, _p, _p, _p, _sz, _p]),
+    "lr_eval_point_sums_f32": (_int, [_p, _p, _i64, C.c_double, _p, _p, _p, _sz, _p]),
+    "lr_eval_listwise": (_int, [_p, _p, _p, _p, _p, _i64, _int, _p, _p]),
+    "lr_eval_coverage_i32": (_int, [_p, _i64, _i64, _p, _p, _p]),
 }
 
 _lib = None

@@ -1237,6 +1237,110 @@ def ivf_search(queries: torch.Tensor, centroids: torch.Tensor, list_ptr: torch.T
 
 
 # --------------------------------------------------------------------------------------
+# evaluation metrics (csrc/eval_metrics.hip): sort keys, rank statistics, pointwise sums, listwise metrics, coverage
+# --------------------------------------------------------------------------------------
+EVAL_SCAN_TILE = 2048       # rows per workgroup of the rank-statistics scan (kScanTile of csrc/eval_metrics.hip)
+EVAL_POINT_TILE = 4096      # rows per workgroup of the pointwise reduction's first stage (kPointTile)
+EVAL_MAX_K = 1024
+EVAL_MAX_ROWS = 2 ** 31 - 1
+
+
+def _eval_rows(n: int, what: str) -> None:
+    if n < 1 or n > EVAL_MAX_ROWS:
+        raise ValueError(f"{what}: shape not supported ({n} rows; 1 .. 2^31 - 1 are)")
+
+
+def eval_keys(score: torch.Tensor, group: Optional[torch.Tensor] = None):
+    """(key int64 [N], bad int32 [1]): key = (group << 32) | the order-preserving image of the f32 score, -0.0 as +0.0
+    (`lr_eval_keys_f32`); `bad` counts the NaN scores.  Groups are int32 >= 0."""
+    _req(score, torch.float32, "score", 1)
+    n = score.numel()
+    _eval_rows(n, "eval_keys")
+    if group is not None:
+        _req(group, torch.int32, "group", 1)
+        if group.numel() != n:
+            raise ValueError("group must have one entry per score")
+    key = torch.empty(n, dtype=torch.int64, device=score.device)
+    bad = torch.empty(1, dtype=torch.int32, device=score.device)
+    _call("lr_eval_keys_f32", _ptr(score), _ptr(group), n, _ptr(key), _ptr(bad), _stream())
+    return key, bad
+
+
+def eval_rank_stats(key_sorted: torch.Tensor, label_sorted: torch.Tensor):
+    """(int64 [3] = num2, P, Nneg; f64 [2] = gauc, pr_auc) over keys sorted ascending with their labels (uint8, != 0 is a
+    positive): `lr_eval_rank_stats`.  With one group ROC AUC = num2 / (2 P Nneg)."""
+    _req(key_sorted, torch.int64, "key_sorted", 1)
+    _req(label_sorted, torch.uint8, "label_sorted", 1)
+    n = key_sorted.numel()
+    _eval_rows(n, "eval_rank_stats")
+    if label_sorted.numel() != n:
+        raise ValueError("label_sorted must have one entry per key")
+    dev = key_sorted.device
+    out_i = torch.empty(3, dtype=torch.int64, device=dev)
+    out_f = torch.empty(2, dtype=torch.float64, device=dev)
+    ws = torch.empty(_lib.load().lr_eval_rank_ws_bytes(n), dtype=torch.uint8, device=dev)
+    _call("lr_eval_rank_stats", _ptr(key_sorted), _ptr(label_sorted), n, _ptr(out_i), _ptr(out_f), _ptr(ws), ws.numel(), _stream())
+    return out_i, out_f
+
+
+def eval_point_sums(pred: torch.Tensor, label: torch.Tensor, mean: float = 0.0):
+    """(f64 [5] = sum (y-p)^2, sum |y-p|, sum y, sum (y-mean)^2, log-loss sum; int64 [4] = TP, TN, P, N of the class rint(p)):
+    `lr_eval_point_sums_f32`, a two-stage reduction in fp64 with a fixed order."""
+    _req(pred, torch.float32, "pred", 1)
+    _req(label, torch.float32, "label", 1)
+    n = pred.numel()
+    _eval_rows(n, "eval_point_sums")
+    if label.numel() != n:
+        raise ValueError("label must have one entry per prediction")
+    dev = pred.device
+    out_f = torch.empty(5, dtype=torch.float64, device=dev)
+    out_i = torch.empty(4, dtype=torch.int64, device=dev)
+    ws = torch.empty(_lib.load().lr_eval_point_ws_bytes(n), dtype=torch.uint8, device=dev)
+    _call("lr_eval_point_sums_f32", _ptr(pred), _ptr(label), n, float(mean), _ptr(out_f), _ptr(out_i), _ptr(ws), ws.numel(),
+          _stream())
+    return out_f, out_i
+
+
+def eval_listwise(reco: torch.Tensor, truth_ptr: torch.Tensor, truth_items: torch.Tensor, truth_len: torch.Tensor,
+                  disc: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """f64 [4, U] = precision, recall, AP and NDCG at k of every user (`lr_eval_listwise`): `reco` int32 [U, k] padded with -1,
+    the truth as a CSR of ascending distinct ids, `truth_len` the divisor of recall, `disc` f64 [k] = 1 / log2(j + 2)."""
+    _req(reco, torch.int32, "reco", 2)
+    U, k = reco.shape
+    if not 1 <= k <= EVAL_MAX_K:
+        raise ValueError(f"eval_listwise: shape not supported (k={k}; 1 .. {EVAL_MAX_K} are)")
+    _eval_rows(U, "eval_listwise")
+    _req(truth_ptr, torch.int64, "truth_ptr", 1)
+    _req(truth_items, torch.int32, "truth_items", 1)
+    _req(truth_len, torch.int32, "truth_len", 1)
+    _req(disc, torch.float64, "disc", 1)
+    if truth_ptr.numel() != U + 1 or truth_len.numel() != U or disc.numel() != k:
+        raise ValueError("truth_ptr must be [U + 1], truth_len [U] and disc [k]")
+    if out is None:
+        out = torch.empty((4, U), dtype=torch.float64, device=reco.device)
+    else:
+        _req(out, torch.float64, "out", 2)
+        if tuple(out.shape) != (4, U):
+            raise ValueError("out must be [4, U] f64")
+    _call("lr_eval_listwise", _ptr(reco), _ptr(truth_ptr), _ptr(truth_items), _ptr(truth_len), _ptr(disc), U, k, _ptr(out),
+          _stream())
+    return out
+
+
+def eval_coverage(reco: torch.Tensor, n_items: int) -> torch.Tensor:
+    """int64 [1]: the number of distinct ids of `reco` (int32, any shape) in [0, n_items); ids < 0 are padding
+    (`lr_eval_coverage_i32`)."""
+    _req(reco, torch.int32, "reco")
+    n, n_items = reco.numel(), int(n_items)
+    _eval_rows(n, "eval_coverage")
+    _eval_rows(n_items, "eval_coverage (n_items)")
+    flags = torch.empty(n_items, dtype=torch.int32, device=reco.device)
+    count = torch.empty(1, dtype=torch.int64, device=reco.device)
+    _call("lr_eval_coverage_i32", _ptr(reco), n, n_items, _ptr(flags), _ptr(count), _stream())
+    return count
+
+
+# --------------------------------------------------------------------------------------
 # streaming in-batch softmax cross-entropy (two-tower retrieval loss)
 # --------------------------------------------------------------------------------------
 # Arithmetic of the two contractions of the streaming softmax cross-entropy: "split_bf16" (default) forms every f32 product as
