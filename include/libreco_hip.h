@@ -1251,6 +1251,38 @@ int lr_autoint_bwd_f32(const float* x, int64_t B, int T, int D, int H, int n_lay
                        float* gparams, void* ws, size_t ws_bytes, lr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Sequence attention — the scaled-dot-product core of libreco/layers/attention.py:5-25 (`tf_attention`, the keras Attention
+ * pooling) and :67-126 (the Keras MultiHeadAttention branch) with the mask of libreco/algorithms/transformer.py:281-328, on
+ * already projected rows: one launch forward, one backward, f32 on the VALU.  Tq, Tk in [1, 64], hd in [1, 128], H in [1, 8],
+ * H * hd <= 256 (lr_seq_attn_supported, otherwise LR_ESHAPE).  No float atomics: same bits from run to run, and a sample's
+ * output and gradients have the same bits at B = 1 and inside any batch.
+ *   q [B, Tq, M], k [B, Tk, M], v [B, Tk, M] contiguous, M = H * hd, head h = columns [h hd, (h + 1) hd).  Per head
+ *     S = (q_h * scale) k_h^T (`scale` as given: 1 / sqrt(hd) for multi-head attention, 1 for tf_attention);
+ *     allowed(b, i, j) = key_ok(b, j) || (causal_or && j <= i); S[i, j] += -1e9f where not allowed — an f32 addition, as keras
+ *     `_masked_softmax` / `_apply_scores` do it, not -inf: a row with nothing allowed is the softmax of the rounded values
+ *     (uniform for |S| < 32) and its gradient still reaches q and k;
+ *     P = softmax(S) over j with the row maximum subtracted; out [B, Tq, M]: O_h = P v_h.
+ *   key_ok(b, j): `key_ok` uint8 [B, Tk] (any pattern, non-zero = valid), or `lens` int32 [B] (j < lens[b]), or both NULL (every
+ *     key valid); both given is LR_EINVAL.  causal_or needs Tq == Tk, otherwise LR_EINVAL (transformer.py:323-328 ORs the
+ *     sequence mask with the causal one).
+ *   `v` may be the pointer `k` (the keys are the values: the pooling form); the forward then reads the rows once where a
+ *     head's columns fit one pass.  gk and gv are always distinct buffers (LR_EINVAL otherwise): the caller adds them.
+ *   forward   writes every element of out.  `saved` (lr_seq_attn_saved_bytes, contents arbitrary on entry) takes every row's
+ *             maximum and sum of exponentials [B, H, Tq, 2]; NULL is inference: nothing but out is written.
+ *   backward  from gout [B, Tq, M], with q, k, v and the masks as the forward saw them and `saved` as it left it: recomputes S
+ *             and P, writes every element of gq [B, Tq, M], gk and gv [B, Tk, M].  No workspace.
+ *   B = 0 writes nothing and returns LR_OK.
+ * ---------------------------------------------------------------------------------- */
+int lr_seq_attn_supported(int Tq, int Tk, int H, int hd);
+size_t lr_seq_attn_saved_bytes(int64_t B, int Tq, int Tk, int H, int hd);
+int lr_seq_attn_fwd_f32(const float* q, const float* k, const float* v, int64_t B, int Tq, int Tk, int H, int hd, float scale,
+                        const uint8_t* key_ok, const int32_t* lens, int causal_or, float* out, void* saved,
+                        size_t saved_bytes, lr_stream_t stream);
+int lr_seq_attn_bwd_f32(const float* q, const float* k, const float* v, int64_t B, int Tq, int Tk, int H, int hd, float scale,
+                        const uint8_t* key_ok, const int32_t* lens, int causal_or, const void* saved, const float* gout,
+                        float* gq, float* gk, float* gv, lr_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Skip-gram word2vec in windows: the training of Item2Vec and DeepWalk, which the reference leaves to
  * gensim.Word2Vec on CPU threads (libreco/bases/gensim_base.py, algorithms/item2vec.py, algorithms/deepwalk.py).  The word
  * index is the item's inner id.  Every random choice is H(seed, stream, a, b) = mix64(mix64(mix64(seed + G stream) + G (a + 1))

@@ -267,6 +267,10 @@ SIGNATURES = {
     "lr_autoint_bwd_ws_bytes": (_sz, [_i64, _int, _int, _int, _int, _p]),
     "lr_autoint_fwd_f32": (_int, [_p, _i64, _int, _int, _int, _int, _p, _int, _p, _p, _sz, _p, _sz, _p, _p]),
     "lr_autoint_bwd_f32": (_int, [_p, _i64, _int, _int, _int, _int, _p, _int, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "lr_seq_attn_supported": (_int, [_int, _int, _int, _int]),
+    "lr_seq_attn_saved_bytes": (_sz, [_i64, _int, _int, _int, _int]),
+    "lr_seq_attn_fwd_f32": (_int, [_p, _p, _p, _i64, _int, _int, _int, _int, _f32, _p, _p, _int, _p, _p, _sz, _p]),
+    "lr_seq_attn_bwd_f32": (_int, [_p, _p, _p, _i64, _int, _int, _int, _int, _f32, _p, _p, _int, _p, _p, _p, _p, _p, _p]),
     "lr_w2v_supported": (_int, [_int]),
     "lr_w2v_walks_i32": (_int, [_p, _i64, _int, _p, _p, _i64, _i64, C.c_uint64, _i64, _p, _p, _p]),
     "lr_w2v_keep_u8": (_int, [_p, _i64, _p, _i64, C.c_uint64, _i64, _p, _p]),

@@ -1,5 +1,6 @@
 """`SIM` (`libreco/algorithms/sim.py`): same constructor and errors; embedding rows and their Adam update on the HIP
-kernels, the search / attention blocks over the (long, short) windows as device torch ops (`nets/seq_nets.py`)."""
+kernels, the exact search unit and the short window's attention in the sequence-attention kernels (csrc/seq_attn.hip), the
+general search unit (scores, top-k, gather) and the projections as device torch ops (`nets/seq_nets.py`)."""
 from __future__ import annotations
 
 import numpy as np

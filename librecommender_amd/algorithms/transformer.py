@@ -1,5 +1,6 @@
 """`Transformer` (`libreco/algorithms/transformer.py`): same constructor and errors; embedding rows and their Adam
-update on the HIP kernels, the small [B, L, D] attention blocks as device torch ops (`nets/seq_nets.py`)."""
+update on the HIP kernels, the attention core of every layer and of the read-out in the sequence-attention kernels
+(csrc/seq_attn.hip), the projections, FFN and norms as device torch ops (`nets/seq_nets.py`)."""
 from __future__ import annotations
 
 from ..bases.base import hip_device

@@ -203,6 +203,16 @@ def dot_attention_torch(q, keys, lens):
     return (torch.softmax(s, dim=1)[:, None, :] @ keys).squeeze(1)
 
 
+def dot_attention(q, keys, lens, fused=True):
+    """`tf_attention` through `lr_seq_attn_fwd/bwd_f32` (one query, one head, scale 1, the keys are the values) where the
+    kernels take the shape and the rows are on the device; `dot_attention_torch` otherwise (`fused=False`, CPU tensors, windows
+    past 64, keys wider than 128)."""
+    if fused and keys.is_cuda and ops.seq_attn_supported(1, keys.shape[1], 1, keys.shape[2]):
+        keys = keys.contiguous()
+        return ops.seq_attn(q[:, None, :], keys, keys, 1, 1.0, lens=lens.to(torch.int32).contiguous()).squeeze(1)
+    return dot_attention_torch(q, keys, lens)
+
+
 def din_attention_torch(q, keys, lens, W1, b1, W2, b2):
     """`din_attention` (layers/attention.py:28-64) in torch ops — used only when the key width
     K' = K*(1+item feats) is not one the fused kernel is compiled for."""
@@ -263,9 +273,11 @@ class FeatDINNet(_FeatNet):
     def __init__(self, spec, embed_size=16, hidden_units=(128, 64, 32), use_bn=True, dropout_rate=0.0,
                  max_seq_len=10, item_sparse_unique=None, item_dense_unique=None,
                  item_dense_cols: Sequence[int] = (), lr=1e-3, epsilon=1e-5, seed=42, device=None,
-                 dense_adam=False, reg=None, use_tf_attention=False, fused_step=True, graph_step=True, **shard):
+                 dense_adam=False, reg=None, use_tf_attention=False, fused_step=True, graph_step=True,
+                 fused_attention=True, **shard):
         super().__init__(spec, embed_size, lr, epsilon, seed, device, dense_adam, reg, **shard)
         self.L = max_seq_len
+        self.fused_attention = bool(fused_attention)         # `use_tf_attention` on the sequence-attention kernels
         dev = self.device
         self.item_sparse = None if item_sparse_unique is None else torch.as_tensor(item_sparse_unique, device=dev).to(torch.int32)
         self.item_dense = None if item_dense_unique is None else torch.as_tensor(item_dense_unique, device=dev, dtype=torch.float32)
@@ -274,7 +286,7 @@ class FeatDINNet(_FeatNet):
         n_id = 0 if self.item_dense is None else self.item_dense.shape[1]
         self.Kp = embed_size * (1 + n_is + n_id)                    # width of an item's "concat" features
         self.pure = n_is == 0 and n_id == 0
-        self.use_tf_attention = bool(use_tf_attention)       # plain dot-product attention: no MLP, torch path
+        self.use_tf_attention = bool(use_tf_attention)       # plain dot-product attention: no MLP
         if not self.use_tf_attention:    # the reference graph has no attention MLP variables in that mode
             self.P.add("attention/attention_layer1/kernel", (4 * self.Kp, 16), "glorot_uniform")
             self.P.add("attention/attention_layer1/bias", (16,), "zeros")
@@ -296,7 +308,7 @@ class FeatDINNet(_FeatNet):
 
     def _attend(self, q, keys, lens, W1, b1, W2, b2):
         if self.use_tf_attention:
-            return dot_attention_torch(q, keys, lens)
+            return dot_attention(q, keys, lens, self.fused_attention)
         if self.kern is not None:        # row-sharded tables: the provider's dense-form attention
             return self.kern.din_attention(q.contiguous(), keys.contiguous(), lens, W1, b1, W2, b2)
         att = din_attention_dense(q, keys, lens, W1, b1, W2, b2)     # item side features: materialised rows, same kernels

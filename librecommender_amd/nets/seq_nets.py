@@ -7,8 +7,12 @@ reference takes for TF >= 2.10: bias-free q / k / v / output projections, scores
 positions pushed down by 1e9) -> swish MLP -> Dense(1).
 
 The embedding rows come from `lr_embed_gather_f32` / `lr_embed_bag_pool_f32` (through `FeatEmbedding`) and go back as
-one (index, gradient) stream into `lr_segments_build` + `lr_embed_scatter_adam_f32`; the [B, L, D] attention blocks
-(L <= ~50) are torch ops on the device — the model is adjacent to the hot path, not on it.
+one (index, gradient) stream into `lr_segments_build` + `lr_embed_scatter_adam_f32`.  The attention cores — every
+Transformer layer and its read-out, SIM's exact search unit and short window — run in `lr_seq_attn_fwd/bwd_f32`
+(csrc/seq_attn.hip): one launch each way on the projected [B, L, M] rows, the mask formed in the kernel from
+`lens` / `top_ok` and the causal flag.  The projections, the FFN and the norms are dense torch matmuls.  With
+`fused_attention=False`, on CPU tensors, for windows past 64 or heads wider than 128 the cores are the torch compositions
+`multi_head_attention` / `dot_attention_torch`, as before.
 """
 from __future__ import annotations
 
@@ -19,9 +23,10 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from .. import ops
 from ..layers import DenseStack, TFDense
 from ..utils.device import to_device
-from .feat_nets import _FeatNet, dot_attention_torch
+from .feat_nets import _FeatNet, dot_attention
 from .fm_nets import _FieldNet
 
 
@@ -66,6 +71,28 @@ def multi_head_attention(q_in, kv_in, Wq, Wk, Wv, Wo, num_heads, mask):
         s = s - 1e9 * (~mask[:, None, :, :]).to(s.dtype)                    # keras `_masked_softmax`
     out = torch.softmax(s, dim=-1) @ v
     return out.transpose(1, 2).reshape(B, Tq, num_heads * hd) @ Wo
+
+
+def fused_multi_head_attention(q_in, kv_in, Wq, Wk, Wv, Wo, num_heads, key_ok_or_lens, causal_or):
+    """`multi_head_attention` with its core (scores, mask, softmax, weighted sum) in `lr_seq_attn_fwd/bwd_f32`; the four
+    projections stay dense matmuls.  `key_ok_or_lens`: None (every key valid), lens [B] (integer: key j < lens[b] is valid) or
+    key_ok [B, Tk] (bool / uint8, any pattern); `causal_or` ORs j <= i into the mask (transformer.py:323-328).  The
+    [B, Tq, Tk] mask is never built."""
+    hd = Wq.shape[1] // num_heads
+    key_ok = lens = None
+    if key_ok_or_lens is not None:
+        if key_ok_or_lens.dim() == 1:
+            lens = key_ok_or_lens.to(torch.int32).contiguous()
+        else:
+            key_ok = key_ok_or_lens.to(torch.uint8).contiguous()
+    out = ops.seq_attn(q_in @ Wq, kv_in @ Wk, kv_in @ Wv, num_heads, 1.0 / math.sqrt(hd), key_ok, lens, causal_or)
+    return out @ Wo
+
+
+def kernel_takes(fused_attention, rows, Tq, Tk, num_heads, head_dim):
+    """The dispatch rule of every attention site: the kernels iff asked for, the rows are on the device and the shape is one
+    they take; otherwise the torch composition (CPU providers, windows past 64, wide heads)."""
+    return bool(fused_attention) and rows.is_cuda and ops.seq_attn_supported(Tq, Tk, num_heads, head_dim)
 
 
 class ItemSeqFeatures:
@@ -130,10 +157,11 @@ class FeatTransformerNet(_FeatNet):
                  max_seq_len=10, num_heads=1, num_tfm_layers=1, positional_embedding="trainable",
                  use_causal_mask=False, feat_agg_mode="concat", item_sparse_unique=None, item_dense_unique=None,
                  item_dense_cols: Sequence[int] = (), lr=1e-3, epsilon=1e-5, seed=42, device=None,
-                 dense_adam=False, reg=None):
+                 dense_adam=False, reg=None, fused_attention=True):
         super().__init__(spec, embed_size, lr, epsilon, seed, device, dense_adam, reg)
         P, K = self.P, embed_size
         self.L, self.H, self.n_layers, self.causal = max_seq_len, num_heads, num_tfm_layers, use_causal_mask
+        self.fused_attention = bool(fused_attention)     # False: every attention block composed from torch ops
         self.seq_feats = ItemSeqFeatures(self, item_sparse_unique, item_dense_unique, item_dense_cols, feat_agg_mode)
         D = self.D = self.seq_feats.dim + K                                  # item feature dim + position dim
         if D % num_heads != 0:
@@ -167,22 +195,25 @@ class FeatTransformerNet(_FeatNet):
         item, seq = feats[:, 0], feats[:, 1:]
         pos = P["transformer/positional_encoding"] if self.trainable_pos else self.pos_const
         x = torch.cat([seq, pos[None].expand(B, -1, -1)], dim=2)
-        key_ok = torch.arange(L, device=self.device)[None, :] < lens[:, None]          # compute_seq_mask
-        mask = key_ok[:, None, :].expand(-1, L, -1)
-        if self.causal:   # transformer.py:323-328: logical OR of the sequence mask and the causal mask
-            mask = mask | torch.ones(L, L, dtype=torch.bool, device=self.device).tril()[None]
+        fused = kernel_takes(self.fused_attention, x, L, L, self.H, self.D // self.H)
+        if not fused:
+            key_ok = torch.arange(L, device=self.device)[None, :] < lens[:, None]      # compute_seq_mask
+            mask = key_ok[:, None, :].expand(-1, L, -1)
+            if self.causal:   # transformer.py:323-328: logical OR of the sequence mask and the causal mask
+                mask = mask | torch.ones(L, L, dtype=torch.bool, device=self.device).tril()[None]
         for l in range(1, self.n_layers + 1):
             s = f"transformer_layer{l}"
             h = rms_norm(x, P[f"{s}/rms_norm_att/scale"])
-            att = multi_head_attention(h, h, P[f"{s}/multi_head_attention/query/kernel"],
-                                       P[f"{s}/multi_head_attention/key/kernel"],
-                                       P[f"{s}/multi_head_attention/value/kernel"],
-                                       P[f"{s}/multi_head_attention/attention_output/kernel"], self.H, mask) + x
+            W = [P[f"{s}/multi_head_attention/{w}/kernel"] for w in ("query", "key", "value", "attention_output")]
+            if fused:         # the kernel forms the same mask from lens and the causal flag
+                att = fused_multi_head_attention(h, h, *W, self.H, lens, self.causal) + x
+            else:
+                att = multi_head_attention(h, h, *W, self.H, mask) + x
             h = rms_norm(att, P[f"{s}/rms_norm_ffn/scale"])
             x = att + gelu(h @ P[f"{s}/ffn/dense/kernel"]) @ P[f"{s}/ffn/dense_1/kernel"]
         x = rms_norm(x, P["rms_norm_last/scale"])
         q = torch.cat([rms_norm(item, P["rms_norm_item/scale"]), torch.ones((B, self.K), device=self.device)], dim=1)
-        return dot_attention_torch(q, x, lens)                                          # layers/attention.py:5-25
+        return dot_attention(q, x, lens, self.fused_attention)                          # layers/attention.py:5-25
 
     def _logits(self, E, seq_out, training):
         return self.out(self.mlp(torch.cat([E.flatten(1), seq_out], dim=1), training)).squeeze(1)
@@ -229,9 +260,10 @@ class FeatSIMNet(_FeatNet):
     def __init__(self, spec, embed_size=16, hidden_units: Sequence[int] = (200, 80), use_bn=True, dropout_rate=0.0,
                  alpha=1.0, beta=1.0, search_topk=10, long_max_len=100, short_max_len=10, num_heads=2,
                  item_sparse_unique=None, item_dense_unique=None, item_dense_cols: Sequence[int] = (), lr=1e-3,
-                 epsilon=1e-5, seed=42, device=None, dense_adam=False, reg=None):
+                 epsilon=1e-5, seed=42, device=None, dense_adam=False, reg=None, fused_attention=True):
         super().__init__(spec, embed_size, lr, epsilon, seed, device, dense_adam, reg)
         P, K = self.P, embed_size
+        self.fused_attention = bool(fused_attention)     # False: both attention blocks composed from torch ops
         if K % num_heads != 0:
             raise AssertionError(f"`item_dim`({K}) should be divisible by `num_heads`({num_heads})")
         self.alpha, self.beta, self.topk, self.Lg, self.S, self.H = alpha, beta, search_topk, long_max_len, short_max_len, num_heads
@@ -258,11 +290,12 @@ class FeatSIMNet(_FeatNet):
         idx = torch.topk(scores.detach(), self.topk, dim=1, sorted=False).indices
         top = torch.gather(long, 1, idx[:, :, None].expand(-1, -1, long.shape[2]))
         top_ok = torch.gather(long_ok, 1, idx)
-        long_out = multi_head_attention(target[:, None, :], top, P["multi_head_attention/query/kernel"],
-                                        P["multi_head_attention/key/kernel"], P["multi_head_attention/value/kernel"],
-                                        P["multi_head_attention/attention_output/kernel"], self.H,
-                                        top_ok[:, None, :]).squeeze(1)
-        short_out = dot_attention_torch(target, short, lens[:, 1])
+        W = [P[f"multi_head_attention/{w}/kernel"] for w in ("query", "key", "value", "attention_output")]
+        if kernel_takes(self.fused_attention, top, 1, self.topk, self.H, self.K // self.H):
+            long_out = fused_multi_head_attention(target[:, None, :], top, *W, self.H, top_ok, False).squeeze(1)
+        else:
+            long_out = multi_head_attention(target[:, None, :], top, *W, self.H, top_ok[:, None, :]).squeeze(1)
+        short_out = dot_attention(target, short, lens[:, 1], self.fused_attention)
         x2 = torch.cat([long_out, short_out, E.flatten(1)], dim=1)
         second = self.second_out(self.second_stage_mlp(x2, training)).squeeze(1)
         if not first:

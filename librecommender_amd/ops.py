@@ -2988,6 +2988,101 @@ def autoint_bwd(x: torch.Tensor, params: torch.Tensor, H: int, head_dims, residu
 
 
 # --------------------------------------------------------------------------------------
+# sequence attention core (csrc/seq_attn.hip)
+# --------------------------------------------------------------------------------------
+def seq_attn_supported(Tq: int, Tk: int, H: int, hd: int) -> bool:
+    """Whether the sequence-attention kernels take `Tq` queries, `Tk` keys and `H` heads of width `hd`."""
+    return bool(_lib.load().lr_seq_attn_supported(int(Tq), int(Tk), int(H), int(hd)))
+
+
+def _seq_attn_check(q, k, v, num_heads, key_ok, lens):
+    """-> (B, Tq, Tk, H, hd) of one sequence-attention call, its operands validated."""
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3:
+            raise ValueError(f"{name} must be a 3-d torch.Tensor")
+    (B, Tq, M), Tk, H = q.shape, k.shape[1], int(num_heads)
+    if k.shape != (B, Tk, M) or v.shape != (B, Tk, M):
+        raise ValueError("k and v must be [B, Tk, M] with q's B and M")
+    if H < 1 or M % H or not seq_attn_supported(Tq, Tk, H, M // H):          # a host query: before any device work
+        raise ValueError(f"unsupported sequence-attention shape: Tq={Tq}, Tk={Tk}, H={H}, M={M} (Tq and Tk from 1 to 64, 1 to 8 "
+                         "heads of width 1 to 128, M at most 256)")
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        _req(t, torch.float32, name, 3)
+    if key_ok is not None and _req(key_ok, torch.uint8, "key_ok", 2).shape != (B, Tk):
+        raise ValueError("key_ok must be [B, Tk]")
+    if lens is not None and _req(lens, torch.int32, "lens", 1).shape != (B,):
+        raise ValueError("lens must be [B]")
+    return B, Tq, Tk, H, M // H
+
+
+def seq_attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: int, scale: float,
+                 key_ok: Optional[torch.Tensor] = None, lens: Optional[torch.Tensor] = None, causal_or: bool = False,
+                 want_saved: bool = True):
+    """`lr_seq_attn_fwd_f32`: softmax((q * scale) k^T + mask) v per head over q [B, Tq, M], k, v [B, Tk, M]; `v` may be `k`
+    itself.  Masked scores get -1e9 added; the mask is `key_ok` uint8 [B, Tk] or `lens` int32 [B] (j < lens[b]), ORed with
+    j <= i under `causal_or`.  Returns (out [B, Tq, M], saved: the opaque bytes `seq_attn_bwd` wants, None without
+    `want_saved`)."""
+    B, Tq, Tk, H, hd = _seq_attn_check(q, k, v, num_heads, key_ok, lens)
+    out = torch.empty((max(B, 1), Tq, H * hd), dtype=torch.float32, device=q.device)[:B]
+    saved = None
+    if want_saved:
+        n = _lib.load().lr_seq_attn_saved_bytes(B, Tq, Tk, H, hd)
+        saved = torch.empty(max(n, 1), dtype=torch.uint8, device=q.device)[:n]
+    _call("lr_seq_attn_fwd_f32", _ptr(q), _ptr(k), _ptr(v), B, Tq, Tk, H, hd, float(scale), _ptr(key_ok), _ptr(lens),
+          int(bool(causal_or)), _ptr(out), _ptr(saved), 0 if saved is None else saved.numel(), _stream())
+    return out, saved
+
+
+def seq_attn_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: int, scale: float, key_ok, lens, causal_or: bool,
+                 saved: torch.Tensor, gout: torch.Tensor):
+    """`lr_seq_attn_bwd_f32`: from gout [B, Tq, M] -> (gq [B, Tq, M], gk, gv [B, Tk, M]); with `v is k` the key gradient is
+    gk + gv."""
+    B, Tq, Tk, H, hd = _seq_attn_check(q, k, v, num_heads, key_ok, lens)
+    if _req(gout, torch.float32, "gout", 3).shape != q.shape:
+        raise ValueError("gout must have q's shape")
+    if _req(saved, torch.uint8, "saved", 1).numel() != _lib.load().lr_seq_attn_saved_bytes(B, Tq, Tk, H, hd):
+        raise ValueError("saved must be the forward's (see `seq_attn_fwd`)")
+    gq = torch.empty((max(B, 1), Tq, H * hd), dtype=torch.float32, device=q.device)[:B]
+    gk = torch.empty((max(B, 1), Tk, H * hd), dtype=torch.float32, device=q.device)[:B]
+    gv = torch.empty((max(B, 1), Tk, H * hd), dtype=torch.float32, device=q.device)[:B]
+    _call("lr_seq_attn_bwd_f32", _ptr(q), _ptr(k), _ptr(v), B, Tq, Tk, H, hd, float(scale), _ptr(key_ok), _ptr(lens),
+          int(bool(causal_or)), _ptr(saved), _ptr(gout), _ptr(gq), _ptr(gk), _ptr(gv), _stream())
+    return gq, gk, gv
+
+
+class _SeqAttn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, num_heads, scale, key_ok, lens, causal_or):
+        shared = v is None                       # the keys are the values
+        q, k = q.contiguous(), k.contiguous()
+        v = k if shared else v.contiguous()
+        grad = any(ctx.needs_input_grad[:3])
+        out, saved = seq_attn_fwd(q, k, v, num_heads, scale, key_ok, lens, causal_or, want_saved=grad)
+        if grad:
+            ctx.save_for_backward(q, k, key_ok, lens, saved, *(() if shared else (v,)))
+            ctx.cfg = (int(num_heads), float(scale), bool(causal_or), shared)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        q, k, key_ok, lens, saved, *rest = ctx.saved_tensors
+        num_heads, scale, causal_or, shared = ctx.cfg
+        v = k if shared else rest[0]
+        gq, gk, gv = seq_attn_bwd(q, k, v, num_heads, scale, key_ok, lens, causal_or, saved, gout.contiguous())
+        if shared:
+            return gq, gk + gv, None, None, None, None, None, None
+        return gq, gk, gv, None, None, None, None, None
+
+
+def seq_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: int, scale: float,
+             key_ok: Optional[torch.Tensor] = None, lens: Optional[torch.Tensor] = None, causal_or: bool = False) -> torch.Tensor:
+    """The scaled-dot-product attention core under autograd: out [B, Tq, M] of `seq_attn_fwd`, gradients to q, k and v from
+    `seq_attn_bwd`.  Passing the same tensor as `k` and `v` (the keys are the values) makes the kernel read the rows once; its
+    gradient is then gk + gv."""
+    return _SeqAttn.apply(q, k, None if v is k else v, num_heads, scale, key_ok, lens, causal_or)
+
+
+# --------------------------------------------------------------------------------------
 # skip-gram word2vec in windows (csrc/word2vec.hip, DESIGN §7.9)
 # --------------------------------------------------------------------------------------
 W2V_NEGATIVES = 5
