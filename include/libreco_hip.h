@@ -1534,6 +1534,35 @@ int lr_ivf_search_f32(const float* queries, int64_t B, const float* centroids, i
                       const int32_t* consumed_idx, const uint8_t* filter_flag, int k, int nprobe, float* out_scores,
                       int64_t* out_ids, void* ws, size_t ws_bytes, lr_stream_t stream);
 
+/* ---- IVF-SQ8 index (csrc/ivf_sq8.hip): the lists of an IVF index as int8 codes + one f32 scale per row, exact re-rank -------
+ * Training and lists are the IVF-Flat entry points above.  Code rows are `code_stride` bytes, D <= code_stride <= 256,
+ * code_stride % 16 == 0, 16-byte aligned; D as above (LR_ESHAPE otherwise, nothing written).  No floating-point atomics.
+ *
+ * lr_ivf_sq8_encode_f32: for j < n, x = rows[list_ids[j]] (rows[j] when list_ids is NULL; an id outside [0, n_rows) reads as a
+ *   zero row): a = max |x_d|, scales[j] = a / 127 (one correctly rounded f32 division), codes[j, d] = clamp(rint(x_d /
+ *   scales[j]), -127, 127) (correctly rounded division, half to even); a == 0 gives scale 0 and codes 0; codes[j, D ..
+ *   code_stride) = 0.  Finite input only.
+ * lr_ivf_sq8_search_f32: lr_ivf_search_f32 with score_j = scales[j] * (sum_d q_d * float(codes[j, d])), the sum in f32 (fma
+ *   chain per lane, then pair sums), the product one rounded f32 multiply; the kk largest by (score desc, global id asc) with the
+ *   same consumed / flag / fill contract.  Envelope: that of lr_ivf_search_f32 with k = kk.  Workspace:
+ *   lr_ivf_sq8_search_ws_bytes (0 outside the envelope), 256-byte aligned.
+ * lr_ivf_sq8_supported: the envelope of search + re-rank for a caller's k and refine: 0 <= refine <= 64, 1 <= k <= 1024 and
+ *   lr_ivf_sq8_search_f32's at kk = refine == 0 ? k : min(k * refine, 1024).
+ * lr_ivf_rerank_f32: per query the candidates cand_ids[b, 0..kk) (global ids; entries outside [0, N), -1 among them, are
+ *   skipped; ids distinct) are scored as f32 inner products with rows[id] and the k largest by (score desc, id asc) written,
+ *   id -1 / score -inf beyond them.  1 <= k, kk <= 1024. */
+int lr_ivf_sq8_supported(int64_t B, int64_t N, int D, int k, int nprobe, int nlist, int refine);
+size_t lr_ivf_sq8_search_ws_bytes(int64_t B, int64_t N, int D, int kk, int nprobe, int nlist);
+int lr_ivf_sq8_encode_f32(const float* rows, int64_t n_rows, int D, const int32_t* list_ids /* [n] or NULL: identity */, int64_t n,
+                          int8_t* codes /* [n, code_stride] */, int code_stride, float* scales /* [n] */, lr_stream_t stream);
+int lr_ivf_sq8_search_f32(const float* queries, int64_t B, const float* centroids, int nlist, const int64_t* list_ptr,
+                          const int32_t* list_ids, const int8_t* codes, int code_stride, const float* scales, int64_t N, int D,
+                          const int64_t* consumed_ptr, const int32_t* consumed_idx, const uint8_t* filter_flag, int kk, int nprobe,
+                          float* out_scores /* [B, kk] */, int64_t* out_ids /* [B, kk] */, void* ws, size_t ws_bytes,
+                          lr_stream_t stream);
+int lr_ivf_rerank_f32(const float* queries, int64_t B, const float* rows, int64_t N, int D, const int64_t* cand_ids /* [B, kk] */,
+                      int kk, int k, float* out_scores /* [B, k] */, int64_t* out_ids /* [B, k] */, lr_stream_t stream);
+
 /* ---- Evaluation metrics (csrc/eval_metrics.hip) — replaces the sklearn / numpy / Python-set work of
  * libreco/evaluation/metrics.py (roc_gauc, precision_at_k, recall_at_k, average_precision_at_k, ndcg_at_k, coverage) and
  * libreco/evaluation/evaluate.py:62-193 (roc_auc_score, precision_recall_curve + auc, log_loss, balanced_accuracy_score,

@@ -200,6 +200,12 @@ SIGNATURES = {
     "lr_ivf_build_lists": (_int, [_p, _i64, _int, _p, _p, _p, _sz, _p]),
     "lr_ivf_centroids_f32": (_int, [_p, _i64, _int, _p, _p, _i64, _int, _p, _p, _sz, _p]),
     "lr_ivf_search_f32": (_int, [_p, _i64, _p, _int, _p, _p, _p, _i64, _int, _p, _p, _p, _int, _int, _p, _p, _p, _sz, _p]),
+    "lr_ivf_sq8_supported": (_int, [_i64, _i64, _int, _int, _int, _int, _int]),
+    "lr_ivf_sq8_search_ws_bytes": (_sz, [_i64, _i64, _int, _int, _int, _int]),
+    "lr_ivf_sq8_encode_f32": (_int, [_p, _i64, _int, _p, _i64, _p, _int, _p, _p]),
+    "lr_ivf_sq8_search_f32": (_int, [_p, _i64, _p, _int, _p, _p, _p, _int, _p, _i64, _int, _p, _p, _p, _int, _int, _p, _p, _p, _sz,
+                                     _p]),
+    "lr_ivf_rerank_f32": (_int, [_p, _i64, _p, _i64, _int, _p, _int, _int, _p, _p, _p]),
     "lr_spmm_csr_f32": (_int, [_p, _p, _p, _i64, _p, _int, _p, _p, _p]),
     "lr_pair_dot_f32": (_int, [_p, _i64, _p, _i64, _int, _p, _p, _i64, _p, _p]),
     "lr_als_supported": (_int, [_int]),

@@ -102,13 +102,18 @@ class EmbedBase(Base):
         return e if item is None else e[self.get_item_id(item)]
 
     # ---- nearest neighbours in embedding space (`embed_base.py:415-551`) ------------------------
-    def init_knn(self, approximate, sim_type, M=100, ef_construction=200, ef_search=200, *, nlist=None, nprobe=None):
+    def init_knn(self, approximate, sim_type, M=100, ef_construction=200, ef_search=200, *, nlist=None, nprobe=None, codes=None,
+                 refine=4):
         """Prepare `search_knn_users / search_knn_items`.  Without `nlist` the search is the exact
         full scan on the MFMA pipe (`lr_score_topk_f32` over unit-normalised rows for "cosine"):
         `approximate=True` (HNSW via nmslib in the reference) is accepted and served exactly;
         `M / ef_construction / ef_search` are ignored.  With `nlist` both sides are searched through an
         IVF-Flat index (`recommendation/ivf.py`) of `nlist` lists (at most the side's row
-        count) built over the same, possibly normalised, rows, `nprobe` (default 1) lists per query."""
+        count) built over the same, possibly normalised, rows, `nprobe` (default 1) lists per query.
+        `codes="sq8"` stores the lists as int8 codes and re-ranks `refine * k` candidates exactly
+        (`recommendation/ivf_sq8.py`); `codes=None` keeps f32 lists."""
+        if codes not in (None, "sq8"):
+            raise ValueError(f"unknown codes: {codes}, only None and `sq8` are supported")
         if sim_type == "cosine":
             self.include_bias = False
         elif sim_type == "inner-product":
@@ -126,10 +131,14 @@ class EmbedBase(Base):
         self._knn_index = {}
         if nlist is not None:
             from ..recommendation.ivf import IVFFlatIndex
+            from ..recommendation.ivf_sq8 import IVFSQ8Index
 
             for side, rows in self._knn_rows.items():
                 nl = min(int(nlist), rows.shape[0])
-                self._knn_index[side] = IVFFlatIndex.train_add(rows, nl, nprobe=min(int(nprobe or 1), nl))
+                if codes == "sq8":
+                    self._knn_index[side] = IVFSQ8Index.train_add(rows, nl, nprobe=min(int(nprobe or 1), nl), refine=refine)
+                else:
+                    self._knn_index[side] = IVFFlatIndex.train_add(rows, nl, nprobe=min(int(nprobe or 1), nl))
 
     def _knn_topk(self, queries, rows, k):
         from .. import ops

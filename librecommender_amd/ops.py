@@ -1237,6 +1237,135 @@ def ivf_search(queries: torch.Tensor, centroids: torch.Tensor, list_ptr: torch.T
 
 
 # --------------------------------------------------------------------------------------
+# IVF-SQ8 index (csrc/ivf_sq8.hip): int8 list codes with one f32 scale per row, scan with fused filter + top-kk, exact re-rank
+# --------------------------------------------------------------------------------------
+IVF_SQ8_MAX_REFINE = 64
+
+
+def ivf_sq8_stride(D: int) -> int:
+    """Bytes of a stored code row: the width rounded up to 16 (one 16-byte load per lane); the padding holds code 0."""
+    return (int(D) + 15) // 16 * 16
+
+
+def ivf_sq8_kk(k: int, refine: int) -> int:
+    """Candidates the scan keeps per query: k without re-rank, else min(max(k, k * refine), 1024)."""
+    return int(k) if int(refine) == 0 else min(max(int(k), int(k) * int(refine)), IVF_MAX_K)
+
+
+def ivf_sq8_encode(rows: torch.Tensor, list_ids: Optional[torch.Tensor] = None):
+    """(codes int8 [n, stride], scales f32 [n]): row j encodes `rows[list_ids[j]]` (`rows[j]` without `list_ids`), gather and
+    encode in one pass (`lr_ivf_sq8_encode_f32`): scale = max|x| / 127, code = clamp(rint(x / scale), -127, 127), a zero row has
+    scale 0."""
+    if not isinstance(rows, torch.Tensor) or rows.dim() != 2:
+        raise ValueError("rows must be a 2-d tensor")
+    n_rows, D = rows.shape
+    _ivf_check_width(D, "ivf_sq8_encode")
+    if n_rows >= 2 ** 31:
+        raise ValueError(f"ivf_sq8_encode: shape not supported (n_rows={n_rows})")
+    _req(rows, torch.float32, "rows", 2)
+    if list_ids is not None:
+        _req(list_ids, torch.int32, "list_ids", 1)
+    n = n_rows if list_ids is None else list_ids.numel()
+    stride = ivf_sq8_stride(D)
+    (rows,) = _ivf_pad(rows)
+    dev = rows.device
+    codes = torch.empty((n, stride), dtype=torch.int8, device=dev)
+    scales = torch.empty(n, dtype=torch.float32, device=dev)
+    _call("lr_ivf_sq8_encode_f32", _ptr(rows), n_rows, rows.shape[1], _ptr(list_ids), n, _ptr(codes), stride, _ptr(scales), _stream())
+    return codes, scales
+
+
+def ivf_sq8_check_search_args(B: int, N: int, D: int, Dq: int, k: int, nprobe: int, nlist: int, refine: int) -> None:
+    """The argument errors of `ivf_sq8_search` and `IVFSQ8Index.search`, raised before a device is needed."""
+    ivf_check_search_args(B, N, D, Dq, k, nprobe, nlist)
+    if refine < 0:
+        raise ValueError(f"refine must be >= 0, got {refine}")
+    if refine > IVF_SQ8_MAX_REFINE or k > IVF_MAX_K:
+        raise ValueError(f"ivf_sq8_search: shape not supported (k={k} refine={refine})")
+
+
+def ivf_sq8_search(queries: torch.Tensor, centroids: torch.Tensor, list_ptr: torch.Tensor, list_ids: torch.Tensor,
+                   codes: torch.Tensor, scales: torch.Tensor, kk: int, nprobe: int, consumed_ptr: Optional[torch.Tensor] = None,
+                   consumed_idx: Optional[torch.Tensor] = None, filter_flag: Optional[torch.Tensor] = None,
+                   out: Optional[tuple] = None):
+    """Stage 1 of the SQ8 search (`lr_ivf_sq8_search_f32`): the `kk` largest `scale_j * dot(q, codes_j)` by (score desc, global
+    id asc) among the rows of the `nprobe` best lists; filter and output contract as `ivf_search`."""
+    if queries.dim() != 2 or centroids.dim() != 2 or codes.dim() != 2:
+        raise ValueError("queries, centroids and codes must be 2-d")
+    B, D = queries.shape
+    N, stride = codes.shape
+    nlist = centroids.shape[0]
+    kk, nprobe = int(kk), int(nprobe)
+    ivf_check_search_args(B, N, centroids.shape[1], D, kk, nprobe, nlist)
+    _ivf_check_width(D, "ivf_sq8_search")
+    if stride != ivf_sq8_stride(D) or list_ptr.numel() != nlist + 1 or list_ids.numel() != N or scales.numel() != N:
+        raise ValueError("centroids / list_ptr / list_ids / scales do not describe codes")
+    Dp = (D + 3) // 4 * 4
+    lib = _lib.load()
+    ws_bytes = lib.lr_ivf_sq8_search_ws_bytes(B, N, Dp, kk, nprobe, nlist) if B > 0 else 0
+    if B > 0 and ws_bytes == 0:
+        raise ValueError(f"ivf_sq8_search: shape not supported (B={B} N={N} D={D} kk={kk} nprobe={nprobe} nlist={nlist})")
+    _req(queries, torch.float32, "queries", 2)
+    _req(centroids, torch.float32, "centroids", 2)
+    _req(codes, torch.int8, "codes", 2)
+    _req(scales, torch.float32, "scales", 1)
+    _req(list_ptr, torch.int64, "list_ptr", 1)
+    _req(list_ids, torch.int32, "list_ids", 1)
+    if consumed_ptr is not None:
+        _req(consumed_ptr, torch.int64, "consumed_ptr", 1)
+        _req(consumed_idx, torch.int32, "consumed_idx", 1)
+    if filter_flag is not None:
+        _req(filter_flag, torch.uint8, "filter_flag", 1)
+    queries, centroids = _ivf_pad(queries, centroids)
+    dev = queries.device
+    if out is None:
+        out_s = torch.empty((B, kk), dtype=torch.float32, device=dev)
+        out_i = torch.empty((B, kk), dtype=torch.int64, device=dev)
+    else:
+        out_s, out_i = _req(out[0], torch.float32, "out scores", 2), _req(out[1], torch.int64, "out ids", 2)
+        if tuple(out_s.shape) != (B, kk) or tuple(out_i.shape) != (B, kk):
+            raise ValueError("out must be ([B, kk] f32, [B, kk] int64)")
+    if B == 0:
+        return out_s, out_i
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    _call("lr_ivf_sq8_search_f32", _ptr(queries), B, _ptr(centroids), nlist, _ptr(list_ptr), _ptr(list_ids), _ptr(codes), stride,
+          _ptr(scales), N, Dp, _ptr(consumed_ptr), _ptr(consumed_idx), _ptr(filter_flag), kk, nprobe, _ptr(out_s), _ptr(out_i),
+          _ptr(ws), ws.numel(), _stream())
+    return out_s, out_i
+
+
+def ivf_rerank(queries: torch.Tensor, rows: torch.Tensor, cand_ids: torch.Tensor, k: int, out: Optional[tuple] = None):
+    """Stage 2 (`lr_ivf_rerank_f32`): the candidates `cand_ids` [B, kk] int64 (global ids, -1 = none) re-scored as f32 inner
+    products with `rows[id]`; the `k` largest by (score desc, id asc), id -1 / score -inf beyond them."""
+    if queries.dim() != 2 or rows.dim() != 2 or cand_ids.dim() != 2 or cand_ids.shape[0] != queries.shape[0]:
+        raise ValueError("queries [B, D], rows [N, D] and cand_ids [B, kk] must be 2-d")
+    B, D = queries.shape
+    N, kk, k = rows.shape[0], cand_ids.shape[1], int(k)
+    if rows.shape[1] != D:
+        raise ValueError(f"queries have width {D}, the rows {rows.shape[1]}")
+    _ivf_check_width(D, "ivf_rerank")
+    if not (1 <= k <= IVF_MAX_K and 1 <= kk <= IVF_MAX_K and 1 <= N < 2 ** 31):
+        raise ValueError(f"ivf_rerank: shape not supported (N={N} kk={kk} k={k})")
+    _req(queries, torch.float32, "queries", 2)
+    _req(rows, torch.float32, "rows", 2)
+    _req(cand_ids, torch.int64, "cand_ids", 2)
+    queries, rows = _ivf_pad(queries, rows)
+    dev = queries.device
+    if out is None:
+        out_s = torch.empty((B, k), dtype=torch.float32, device=dev)
+        out_i = torch.empty((B, k), dtype=torch.int64, device=dev)
+    else:
+        out_s, out_i = _req(out[0], torch.float32, "out scores", 2), _req(out[1], torch.int64, "out ids", 2)
+        if tuple(out_s.shape) != (B, k) or tuple(out_i.shape) != (B, k):
+            raise ValueError("out must be ([B, k] f32, [B, k] int64)")
+    if B == 0:
+        return out_s, out_i
+    _call("lr_ivf_rerank_f32", _ptr(queries), B, _ptr(rows), N, rows.shape[1], _ptr(cand_ids), kk, k, _ptr(out_s), _ptr(out_i),
+          _stream())
+    return out_s, out_i
+
+
+# --------------------------------------------------------------------------------------
 # evaluation metrics (csrc/eval_metrics.hip): sort keys, rank statistics, pointwise sums, listwise metrics, coverage
 # --------------------------------------------------------------------------------------
 EVAL_SCAN_TILE = 2048       # rows per workgroup of the rank-statistics scan (kScanTile of csrc/eval_metrics.hip)

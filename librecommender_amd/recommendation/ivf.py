@@ -46,6 +46,21 @@ class IVFFlatIndex:
         self.timings = {}
 
     # ---- build ------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def train_centroids(rows_p: torch.Tensor, nlist: int, niter: int) -> torch.Tensor:
+        """The k-means of `train_add` over padded rows (shared with `IVFSQ8Index`): centroids [nlist, D]."""
+        N, dev = rows_p.shape[0], rows_p.device
+        n_train = min(N, TRAIN_CAP * nlist)
+        if n_train == N:
+            tr = rows_p
+        else:
+            tr = rows_p.index_select(0, (torch.arange(n_train, dtype=torch.int64, device=dev) * N) // n_train).contiguous()
+        cent = tr.index_select(0, (torch.arange(nlist, dtype=torch.int64, device=dev) * n_train) // nlist).contiguous()
+        for _ in range(niter):
+            ptr, ids = ops.ivf_build_lists(ops.ivf_assign(tr, cent), nlist)
+            ops.ivf_centroids(tr, ptr, ids, cent)
+        return cent
+
     @classmethod
     def train_add(cls, rows: torch.Tensor, nlist: int, niter: int = 20, nprobe: int = 1, timings: bool = False) -> "IVFFlatIndex":
         """k-means on at most `256 * nlist` rows (ids floor(j N / n_train); initial centroids the training rows at
@@ -58,9 +73,7 @@ class IVFFlatIndex:
         if not 1 <= int(nprobe) <= nlist:
             raise ValueError(f"nprobe must be in 1..nlist ({nlist}), got {nprobe}")
         ops._req(rows, torch.float32, "rows", 2)
-        dev = rows.device
         (rows_p,) = ops._ivf_pad(rows)
-        n_train = min(N, TRAIN_CAP * nlist)
         t = {}
 
         def timed(name, fn):
@@ -74,18 +87,7 @@ class IVFFlatIndex:
             t[name] = t.get(name, 0.0) + a.elapsed_time(b)
             return out
 
-        def train():
-            if n_train == N:
-                tr = rows_p
-            else:
-                tr = rows_p.index_select(0, (torch.arange(n_train, dtype=torch.int64, device=dev) * N) // n_train).contiguous()
-            cent = tr.index_select(0, (torch.arange(nlist, dtype=torch.int64, device=dev) * n_train) // nlist).contiguous()
-            for _ in range(niter):
-                ptr, ids = ops.ivf_build_lists(ops.ivf_assign(tr, cent), nlist)
-                ops.ivf_centroids(tr, ptr, ids, cent)
-            return cent
-
-        cent = timed("train_ms", train)
+        cent = timed("train_ms", lambda: cls.train_centroids(rows_p, nlist, niter))
         list_of = timed("assign_ms", lambda: ops.ivf_assign(rows_p, cent))
         list_ptr, list_ids, list_rows = timed("permute_ms", lambda: ops.ivf_build_lists(list_of, nlist, rows_p))
         index = cls(cent, list_ptr, list_ids, list_rows, nprobe, D)
@@ -120,8 +122,16 @@ class IVFFlatIndex:
         """The index of `save` over `rows`, the same [N, d] catalogue (default: `item_embed.json` of the same serving
         directory, as `serving.save_embed` writes it)."""
         with np.load(os.path.join(path, INDEX_FILE)) as z:
-            cent, ptr, ids = z["centroids"], z["list_ptr"], z["list_ids"]
-            nprobe, d = int(z["nprobe"]), int(z["d"])
+            cent_t, list_ptr, list_ids, rows_p, nprobe, d = cls.read_lists(z, path, device, rows, INDEX_FILE)
+        list_rows = ops.embed_gather(rows_p, list_ids)
+        return cls(cent_t, list_ptr, list_ids, list_rows, nprobe, d)
+
+    @staticmethod
+    def read_lists(z, path: str, device, rows: Optional[torch.Tensor], name: str):
+        """What `load` reads and checks of an opened index file `z` (shared with `IVFSQ8Index`): (centroids, list_ptr, list_ids,
+        the padded rows on the device, nprobe, d)."""
+        cent, ptr, ids = z["centroids"], z["list_ptr"], z["list_ids"]
+        nprobe, d = int(z["nprobe"]), int(z["d"])
         if rows is None:
             import json
 
@@ -129,14 +139,13 @@ class IVFFlatIndex:
                 ie = json.load(f)
             rows = torch.tensor([ie[str(i)] for i in range(len(ie))], dtype=torch.float32)
         if rows.dim() != 2 or rows.shape[1] != d or rows.shape[0] != ids.shape[0] or cent.shape[1] != d:
-            raise ValueError("ivf_index.npz does not describe these rows")
+            raise ValueError(f"{name} does not describe these rows")
         if (ptr.shape[0] != cent.shape[0] + 1 or int(ptr[0]) != 0 or int(ptr[-1]) != ids.shape[0] or (np.diff(ptr) < 0).any()
                 or (ids.size and (ids.min() < 0 or ids.max() >= ids.shape[0]))):
-            raise ValueError("ivf_index.npz is inconsistent")
+            raise ValueError(f"{name} is inconsistent")
         dev = torch.device(device)
         rows = ops._req(rows.to(dev), torch.float32, "rows", 2)
         cent_t, rows_p = ops._ivf_pad(torch.from_numpy(np.ascontiguousarray(cent, dtype=np.float32)).to(dev))[0], ops._ivf_pad(rows)[0]
         list_ids = torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int32)).to(dev)
-        list_rows = ops.embed_gather(rows_p, list_ids)
-        return cls(cent_t.contiguous(), torch.from_numpy(np.ascontiguousarray(ptr, dtype=np.int64)).to(dev), list_ids, list_rows,
-                   nprobe, d)
+        return (cent_t.contiguous(), torch.from_numpy(np.ascontiguousarray(ptr, dtype=np.int64)).to(dev), list_ids, rows_p,
+                nprobe, d)

@@ -9,7 +9,8 @@ With `use_index=True` (the default) and an `ivf_index.npz` in the directory (`se
 `faiss_index.bin`) `recommend` goes through the IVF-Flat index instead (`lr_ivf_search_f32`): the probed lists are
 scanned with the consumed ids filtered inside the kernel, which equals the reference's "search n_rec + len(consumed), drop
 consumed, take n_rec" whenever the probed lists hold that many rows (where they hold fewer, the reference answers with fewer
-than n_rec items and this search still returns what the lists hold)."""
+than n_rec items and this search still returns what the lists hold).  Without that file an `ivf_sq8_index.npz`
+(`serving.save_ivf_sq8_index`) is used the same way: int8 lists, exact re-rank from the item table held here."""
 from __future__ import annotations
 
 import json
@@ -51,6 +52,9 @@ class EmbedServer:
         if use_index and os.path.exists(os.path.join(path, "ivf_index.npz")):
             from ..recommendation.ivf import IVFFlatIndex
             self.index = IVFFlatIndex.load(path, self.device, self.item_embeds)
+        elif use_index and os.path.exists(os.path.join(path, "ivf_sq8_index.npz")):      # the Flat file wins when both exist
+            from ..recommendation.ivf_sq8 import IVFSQ8Index
+            self.index = IVFSQ8Index.load(path, self.device, self.item_embeds)
 
     def recommend(self, users: Sequence, n_rec: int) -> Dict[object, List]:
         """{raw user: [raw item ids]}: the `n_rec` highest inner products among the items the user has not consumed

@@ -121,9 +121,28 @@ def save_ivf_index(path: str, model, nlist: int = 80, nprobe: int = 10):
     """The reference's `save_faiss_index` (`embed.py:42-54`: `IndexIVFFlat(IndexFlatIP, d, nlist, METRIC_INNER_PRODUCT)`, trained
     on and filled with `model.item_embeds[: n_items]`), as this library's own index (`recommendation/ivf.py`):
     `<path>/ivf_index.npz` holds centroids, list_ptr, list_ids, nprobe and d.  faiss's binary format is not written."""
+    from ..recommendation.ivf import IVFFlatIndex
+
+    index = IVFFlatIndex.train_add(_index_items(path, model, nlist, nprobe), nlist, nprobe=nprobe)
+    return index.save(path)
+
+
+def save_ivf_sq8_index(path: str, model, nlist: int = 80, nprobe: int = 10, refine: int = 4):
+    """`save_ivf_index` for the scalar-quantised index (`recommendation/ivf_sq8.py`): `<path>/ivf_sq8_index.npz`
+    holds centroids, list_ptr, list_ids, nprobe, refine and d, and no codes.  `EmbedServer` uses it when no `ivf_index.npz`
+    lies beside it."""
+    from ..recommendation.ivf_sq8 import IVFSQ8Index, check_refine
+
+    check_refine(refine)
+    index = IVFSQ8Index.train_add(_index_items(path, model, nlist, nprobe), nlist, nprobe=nprobe, refine=refine)
+    return index.save(path)
+
+
+def _index_items(path: str, model, nlist, nprobe):
+    """The f32 item rows an index file is built over, after the argument checks that need no device."""
     import torch
 
-    from ..recommendation.ivf import IVFFlatIndex, check_train_args
+    from ..recommendation.ivf import check_train_args
 
     _ensure_dir(path)
     items = model.item_embeds
@@ -134,5 +153,4 @@ def save_ivf_index(path: str, model, nlist: int = 80, nprobe: int = 10):
     check_train_args(items.shape[0], items.shape[1], int(nlist), 20)
     if not 1 <= int(nprobe) <= int(nlist):
         raise ValueError(f"nprobe must be in 1..nlist ({nlist}), got {nprobe}")
-    index = IVFFlatIndex.train_add(items.to(torch.float32).contiguous(), nlist, nprobe=nprobe)
-    return index.save(path)
+    return items.to(torch.float32).contiguous()
