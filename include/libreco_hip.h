@@ -1272,9 +1272,22 @@ int lr_autoint_bwd_f32(const float* x, int64_t B, int T, int D, int H, int n_lay
  *   backward  from gout [B, Tq, M], with q, k, v and the masks as the forward saw them and `saved` as it left it: recomputes S
  *             and P, writes every element of gq [B, Tq, M], gk and gv [B, Tk, M].  No workspace.
  *   B = 0 writes nothing and returns LR_OK.
+ *   lr_seq_attn_plan_params   the launch plan of a forward (bwd = 0) or backward (bwd != 0) call of this shape, as the launch
+ *             itself derives it; `aligned`: whether every pointer of the call is on a 16-byte boundary.  Host only, launches
+ *             nothing; for tests that assert the branch they run.  LR_ESHAPE for an unsupported shape, LR_EINVAL for B < 1 or
+ *             a null out8.  out8 = {
+ *               TB         units (sample, head) per workgroup, 1 .. 64; the grid is ceil(B H / TB) workgroups,
+ *               nch        column chunks per head (hd <= nch CW),
+ *               CW         columns per chunk (a multiple of 4 where nch > 1; the last chunk holds hd - (nch - 1) CW),
+ *               CS         LDS stride of a chunk row in floats, 4 (ceil(CW / 4) | 1),
+ *               ST         LDS stride of a score row in floats, Tk | 1,
+ *               G          lanes per softmax row, 1, 2, 4 or 8 (from Tk alone),
+ *               vec        1: rows move 16 bytes at a time (hd % 4 == 0 and aligned), 0: float by float,
+ *               lds_bytes  dynamic LDS of a workgroup, at most 65536 }
  * ---------------------------------------------------------------------------------- */
 int lr_seq_attn_supported(int Tq, int Tk, int H, int hd);
 size_t lr_seq_attn_saved_bytes(int64_t B, int Tq, int Tk, int H, int hd);
+int lr_seq_attn_plan_params(int64_t B, int Tq, int Tk, int H, int hd, int bwd, int aligned, int32_t* out8);
 int lr_seq_attn_fwd_f32(const float* q, const float* k, const float* v, int64_t B, int Tq, int Tk, int H, int hd, float scale,
                         const uint8_t* key_ok, const int32_t* lens, int causal_or, float* out, void* saved,
                         size_t saved_bytes, lr_stream_t stream);

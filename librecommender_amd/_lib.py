@@ -14,7 +14,7 @@ from pathlib import Path
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "liblibreco_hip.so"
 
 LR_OK, LR_EINVAL, LR_ESHAPE, LR_EWORKSPACE = 0, -1, -2, -3
-ABI_VERSION = 25        # == lr_abi_version() of the library these signatures were written for
+ABI_VERSION = 26        # == lr_abi_version() of the library these signatures were written for
 
 COMBINERS = {"sum": 0, "mean": 1, "sqrtn": 2}
 
@@ -275,6 +275,7 @@ SIGNATURES = {
     "lr_autoint_bwd_f32": (_int, [_p, _i64, _int, _int, _int, _int, _p, _int, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "lr_seq_attn_supported": (_int, [_int, _int, _int, _int]),
     "lr_seq_attn_saved_bytes": (_sz, [_i64, _int, _int, _int, _int]),
+    "lr_seq_attn_plan_params": (_int, [_i64, _int, _int, _int, _int, _int, _int, _p]),
     "lr_seq_attn_fwd_f32": (_int, [_p, _p, _p, _i64, _int, _int, _int, _int, _f32, _p, _p, _int, _p, _p, _sz, _p]),
     "lr_seq_attn_bwd_f32": (_int, [_p, _p, _p, _i64, _int, _int, _int, _int, _f32, _p, _p, _int, _p, _p, _p, _p, _p, _p]),
     "lr_w2v_supported": (_int, [_int]),

@@ -370,6 +370,22 @@ extern "C" size_t lr_seq_attn_saved_bytes(int64_t B, int Tq, int Tk, int H, int 
   return static_cast<size_t>(B) * H * Tq * 2 * sizeof(float);          // every row's maximum and sum of exponentials
 }
 
+// The launch plan of a call, from the launches' own sa_args and sa_lds_bytes.  Host only.
+extern "C" int lr_seq_attn_plan_params(int64_t B, int Tq, int Tk, int H, int hd, int bwd, int aligned, int32_t* out8) {
+  if (!sa_shape_ok(Tq, Tk, H, hd)) return LR_ESHAPE;
+  LR_CHECK_ARG(B >= 1 && out8 != nullptr);
+  const SaArgs a = sa_args(B, Tq, Tk, H, hd, 1.f, 0, 0, bwd != 0, aligned != 0);
+  out8[0] = a.TB;
+  out8[1] = a.nch;
+  out8[2] = a.CW;
+  out8[3] = a.CS;
+  out8[4] = a.ST;
+  out8[5] = a.G;
+  out8[6] = a.vec;
+  out8[7] = static_cast<int32_t>(sa_lds_bytes(a, a.TB, bwd != 0));
+  return LR_OK;
+}
+
 extern "C" int lr_seq_attn_fwd_f32(const float* q, const float* k, const float* v, int64_t B, int Tq, int Tk, int H, int hd,
                                    float scale, const uint8_t* key_ok, const int32_t* lens, int causal_or, float* out,
                                    void* saved, size_t saved_bytes, lr_stream_t stream) {

@@ -3124,6 +3124,22 @@ def seq_attn_supported(Tq: int, Tk: int, H: int, hd: int) -> bool:
     return bool(_lib.load().lr_seq_attn_supported(int(Tq), int(Tk), int(H), int(hd)))
 
 
+_SEQ_ATTN_PLAN = ("TB", "nch", "CW", "CS", "ST", "G", "vec", "lds_bytes")
+
+
+def seq_attn_plan(B: int, Tq: int, Tk: int, H: int, hd: int, bwd: bool, aligned: bool = True) -> dict:
+    """`lr_seq_attn_plan_params`: the launch plan of a forward (`bwd` false) or backward call of this shape, as the launch
+    derives it (a host query): units per workgroup `TB`, `nch` chunks of `CW` columns per head, the LDS strides `CS` and
+    `ST`, `G` lanes per softmax row, `vec` (16-byte row moves; 0 with `aligned=False`: some pointer off a 16-byte boundary)
+    and `lds_bytes`."""
+    import ctypes as C
+
+    out = (C.c_int32 * 8)()
+    check(_lib.load().lr_seq_attn_plan_params(int(B), int(Tq), int(Tk), int(H), int(hd), int(bool(bwd)), int(bool(aligned)), out),
+          "lr_seq_attn_plan_params")
+    return dict(zip(_SEQ_ATTN_PLAN, (int(x) for x in out)))
+
+
 def _seq_attn_check(q, k, v, num_heads, key_ok, lens):
     """-> (B, Tq, Tk, H, hd) of one sequence-attention call, its operands validated."""
     for name, t in (("q", q), ("k", k), ("v", v)):

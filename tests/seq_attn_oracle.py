@@ -105,12 +105,55 @@ CASES = [
     (131, 10, 10, 1, 32, "lens", False, False),      # a batch that is no multiple of any tile
     (131, 1, 10, 1, 32, "lens", False, True),        # the same for the pooling form
     (6, 5, 5, 2, 8, None, False, False),             # no mask at all
+    # Appended (CASES[3], [5], [10] and [11] are used by index): the launch plans past one unit per workgroup and one chunk per
+    # head.  tests/test_seq_attn_cpu.py pins the plan of each (`PLANS`) and asks the union of `plan_class` for every branch.
+    (345, 3, 3, 3, 4, "lens", False, False),         # TB 2: tiles that mix two samples (H odd), a last tile of one unit
+    (345, 4, 9, 3, 8, "u8", False, False),           # TB 2, G 2: Tq != Tk, a per-sample u8 mask inside a tile
+    (345, 6, 6, 3, 8, "lens", True, False),          # TB 2: causal OR lens inside a tile
+    (4099, 5, 5, 8, 4, "lens", False, False),        # TB 64 (the cap), a last tile of 24 units
+    (4099, 1, 7, 8, 4, "lens", False, True),         # TB 64, the pooling form: the key chunk serves as the values
+    (1537, 40, 40, 1, 32, "lens", False, False),     # the LDS clamp: TB 3 forward, 2 backward; G 8
+    (1300, 1, 20, 1, 16, "lens", False, True),       # TB 2, G 4, the pooling form
+    (3, 20, 20, 1, 8, "lens", False, False),         # G 4 with Tq > 1
+    (2, 64, 64, 1, 64, "lens", True, False),         # one chunk forward, two of 32 backward
+    (2, 64, 64, 1, 128, "lens", False, False),       # two chunks of 64 forward; 44, 44, 40 backward
+    (2, 64, 64, 1, 99, "lens", False, False),        # the scalar path, chunks of 52 and 47
+    (2, 64, 64, 1, 61, "lens", False, False),        # scalar, chunked only backward: 32 and 29
+    (1, 64, 64, 2, 128, "u8", False, True),          # v is k with more than one chunk (no reuse), the second head at M = 256
+    (2, 63, 61, 1, 128, "lens", False, False),       # an unpaired row in `sa_apply`, a clamped key tile in `sa_dots`
 ]
 WIDE = CASES[10]
+TILE_MIXED, TILE_CAP, TILE_CAP_POOLED, TILE_CLAMPED = CASES[13], CASES[16], CASES[17], CASES[18]
+U8_TILED, CHUNKED = CASES[14], CASES[22]
 
 
 def sid(c):
     return "x".join("-" if x is None else str(int(x)) if isinstance(x, bool) else str(x) for x in c)
+
+
+def plan_class(args):
+    """The branches of csrc/seq_attn.hip that a case of `CASES` runs, from the launches' own plan (`ops.seq_attn_plan`, a
+    host query), as a set of names.  More than one unit per workgroup together with more than one chunk cannot occur: a unit
+    that needs two chunks takes more than half the LDS budget, so no second unit fits beside it."""
+    from librecommender_amd import ops
+
+    B, Tq, Tk, H, hd, _, _, shared = args
+    fwd, bwd = ops.seq_attn_plan(B, Tq, Tk, H, hd, False), ops.seq_attn_plan(B, Tq, Tk, H, hd, True)
+    out = {f"G={fwd['G']}"}
+    for p in (fwd, bwd):
+        out.add("TB=1" if p["TB"] == 1 else "TB=64" if p["TB"] == 64 else "1<TB<64")
+        out.add(f"nch={p['nch']}")
+        if (B * H) % p["TB"]:
+            out.add("ragged last tile")
+        if p["nch"] > 1 and (hd - (p["nch"] - 1) * p["CW"]) % 4:
+            out.add("last chunk cw%4!=0")
+        if p["nch"] > 1 and shared:
+            out.add("shared, nch>1")
+    if fwd["TB"] != bwd["TB"]:
+        out.add("TB fwd!=bwd")
+    if fwd["nch"] != bwd["nch"]:
+        out.add("nch fwd!=bwd")
+    return out
 
 
 @functools.lru_cache(maxsize=None)

@@ -61,7 +61,7 @@ def test_symbols_are_bound_and_declared():
     lib = _lib.load()
     for name in SYMBOLS:
         assert name in _lib.SIGNATURES and re.search(rf"\b{name}\s*\(", header) and hasattr(lib, name)
-    assert _lib.ABI_VERSION == 25
+    assert _lib.ABI_VERSION == 26
     # host-only entry points: the envelope and the workspace sizes
     assert lib.lr_ivf_supported(1, 10_000_000, 128, 100, 32, 12649) == 1
     assert lib.lr_ivf_supported(1024, 100_000_000, 128, 100, 128, 40000) == 1

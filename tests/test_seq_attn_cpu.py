@@ -1,6 +1,9 @@
 """The sequence-attention oracle (tests/seq_attn_oracle.py) against torch autograd in fp64 of the two compositions the kernels
 replace (`seq_nets.multi_head_attention`'s core and `feat_nets.dot_attention_torch`), the f32 semantics of a row with nothing
-allowed, the host queries of csrc/seq_attn.hip, and the argument errors of `ops.seq_attn` that need no device."""
+allowed, the host queries of csrc/seq_attn.hip (the launch plan among them: its invariants over the whole envelope, the plan
+of every case written for a branch, and that the cases reach every branch), and the argument errors of `ops.seq_attn` that
+need no device."""
+import ctypes as C
 import math
 
 import numpy as np
@@ -36,9 +39,10 @@ def test_oracle_equals_autograd_of_multi_head_attention(args):
     assert O.max_diff(q.grad.numpy(), gq) <= 1e-12 and O.max_diff(kv.grad.numpy(), gk + gv) <= 1e-12
 
 
-@pytest.mark.parametrize("args", [O.CASES[3], O.CASES[4], O.CASES[5]], ids=O.sid)
+@pytest.mark.parametrize("args", [O.CASES[3], O.CASES[4], O.CASES[5], O.CASES[25]], ids=O.sid)
 def test_oracle_gk_and_gv_apart(args):
-    """Values that are not the keys: the same composition written out with three inputs, so gk and gv are pinned one by one."""
+    """Values that are not the keys: the same composition written out with three inputs, so gk and gv are pinned one by one
+    (also where the case's values are its keys, on several heads with a u8 mask: no pooling form)."""
     c = O.case(*args)
     B, Tq, Tk, H, hd = c["shape"]
     q, k, v = _t(c["q"]), _t(c["k"]), _t(c["v"])
@@ -53,8 +57,9 @@ def test_oracle_gk_and_gv_apart(args):
         assert O.max_diff(got.numpy(), want[name]) <= 1e-12, name
 
 
-@pytest.mark.parametrize("args", [c for c in O.CASES if c[7] and c[0] <= 6], ids=O.sid)
+@pytest.mark.parametrize("args", [c for c in O.CASES if c[7] and c[0] <= 6 and c[1] == c[3] == 1 and c[5] == "lens"], ids=O.sid)
 def test_oracle_equals_autograd_of_dot_attention(args):
+    """The pooling form: one query, one head, a length mask."""
     c = O.case(*args)
     q, keys = _t(c["q"][:, 0]), _t(c["k"])
     out = dot_attention_torch(q, keys, torch.from_numpy(c["lens"]))
@@ -103,6 +108,111 @@ def test_host_queries():
                     ((4, 4, 8, 8), (4, 4, 9, 8)), ((4, 4, 8, 32), (4, 4, 8, 33))):
         assert lib.lr_seq_attn_saved_bytes(3, *ok) > 0 and lib.lr_seq_attn_saved_bytes(3, *bad) == 0
     assert lib.lr_seq_attn_saved_bytes(0, 4, 4, 1, 8) == 0 and lib.lr_seq_attn_saved_bytes(-1, 4, 4, 1, 8) == 0
+
+
+# ---- the launch plan (`lr_seq_attn_plan_params`, `ops.seq_attn_plan`): what the launches themselves derive ------------
+def _plan(lib, B, Tq, Tk, H, hd, bwd, aligned=1):
+    out = (C.c_int32 * 8)()
+    assert lib.lr_seq_attn_plan_params(B, Tq, Tk, H, hd, bwd, aligned, out) == 0, (B, Tq, Tk, H, hd, bwd)
+    return tuple(out)
+
+
+def test_plan_invariants_over_the_whole_envelope():
+    """Every Tq = Tk in 1 .. 64 and hd in 1 .. 128, forward and backward, one head, a batch of one sample and one that asks
+    for the cap of 64 units per workgroup: the tile fits 64 KB, the chunks cover the head's columns exactly once, chunks start
+    on a multiple of 4 columns, the strides are what the kernels' bank-conflict reasoning assumes, and G is Tk's alone."""
+    lib = _lib.load()
+    up4 = lambda n: (n + 3) & ~3
+    tiled = chunked = 0
+    for T in range(1, 65):
+        groups = set()
+        for hd in range(1, 129):
+            for B in (1, 40000):
+                for bwd in (0, 1):
+                    TB, nch, CW, CS, ST, G, vec, lds = _plan(lib, B, T, T, 1, hd, bwd)
+                    what = (B, T, hd, bwd)
+                    assert lds <= 65536 and 1 <= TB <= 64, what
+                    assert (nch - 1) * CW < hd <= nch * CW, what
+                    assert nch == 1 or CW % 4 == 0, what
+                    assert CS % 4 == 0 and (CS // 4) % 2 == 1 and CS >= up4(CW), what
+                    assert ST == T | 1 and vec == (hd % 4 == 0), what
+                    assert _plan(lib, B, T, T, 1, hd, bwd, 0)[:6] == (TB, nch, CW, CS, ST, G), what    # alignment moves `vec` alone
+                    assert TB == 1 or (B > 1 and nch == 1), what       # a unit that needs two chunks leaves no room for a second
+                    groups.add(G)
+                    tiled += TB > 1
+                    chunked += nch > 1
+        assert groups == {1 if T <= 8 else 2 if T <= 16 else 4 if T <= 32 else 8}, T
+    assert tiled and chunked
+
+
+def test_plan_errors():
+    lib = _lib.load()
+    out = (C.c_int32 * 8)(*([7] * 8))
+    for bad in ((65, 4, 1, 8), (4, 65, 1, 8), (4, 4, 1, 129), (4, 4, 9, 8), (4, 4, 8, 33), (0, 4, 1, 8), (4, 4, 1, 0)):
+        assert lib.lr_seq_attn_plan_params(3, *bad, 0, 1, out) == _lib.LR_ESHAPE, bad
+        with pytest.raises(ValueError, match="lr_seq_attn_plan_params"):
+            ops.seq_attn_plan(3, *bad, False)
+    for B in (0, -1):
+        assert lib.lr_seq_attn_plan_params(B, 4, 4, 1, 8, 0, 1, out) == _lib.LR_EINVAL
+        assert lib.lr_seq_attn_plan_params(B, 4, 4, 1, 8, 1, 1, out) == _lib.LR_EINVAL
+    assert lib.lr_seq_attn_plan_params(3, 4, 4, 1, 8, 0, 1, None) == _lib.LR_EINVAL
+    assert list(out) == [7] * 8                                            # an error writes nothing
+    assert lib.lr_seq_attn_plan_params(3, 4, 4, 1, 8, 0, 1, out) == 0 and out[0] == 1
+    with pytest.raises(ValueError, match="lr_seq_attn_plan_params"):
+        ops.seq_attn_plan(0, 4, 4, 1, 8, True)
+    p = ops.seq_attn_plan(3, 4, 9, 2, 8, True)
+    assert list(p) == ["TB", "nch", "CW", "CS", "ST", "G", "vec", "lds_bytes"] and p["vec"] == 1 and p["ST"] == 9 and p["G"] == 2
+    assert ops.seq_attn_plan(3, 4, 9, 2, 8, True, aligned=False)["vec"] == 0 and ops.seq_attn_plan(3, 4, 9, 2, 7, True)["vec"] == 0
+
+
+# (TB, nch, CW) forward and backward of every case appended to `O.CASES` for its plan: a change to the heuristics or to the
+# number of compute units they assume that moves a case off the branch it was written for fails here, by name
+PLANS = {
+    (345, 3, 3, 3, 4, "lens", False, False): ((2, 1, 4), (2, 1, 4)),
+    (345, 4, 9, 3, 8, "u8", False, False): ((2, 1, 8), (2, 1, 8)),
+    (345, 6, 6, 3, 8, "lens", True, False): ((2, 1, 8), (2, 1, 8)),
+    (4099, 5, 5, 8, 4, "lens", False, False): ((64, 1, 4), (64, 1, 4)),
+    (4099, 1, 7, 8, 4, "lens", False, True): ((64, 1, 4), (64, 1, 4)),
+    (1537, 40, 40, 1, 32, "lens", False, False): ((3, 1, 32), (2, 1, 32)),
+    (1300, 1, 20, 1, 16, "lens", False, True): ((2, 1, 16), (2, 1, 16)),
+    (3, 20, 20, 1, 8, "lens", False, False): ((1, 1, 8), (1, 1, 8)),
+    (2, 64, 64, 1, 64, "lens", True, False): ((1, 1, 64), (1, 2, 32)),
+    (2, 64, 64, 1, 128, "lens", False, False): ((1, 2, 64), (1, 3, 44)),
+    (2, 64, 64, 1, 99, "lens", False, False): ((1, 2, 52), (1, 2, 52)),
+    (2, 64, 64, 1, 61, "lens", False, False): ((1, 1, 61), (1, 2, 32)),
+    (1, 64, 64, 2, 128, "u8", False, True): ((1, 2, 64), (1, 3, 44)),
+    (2, 63, 61, 1, 128, "lens", False, False): ((1, 2, 64), (1, 2, 64)),
+}
+# what else the cases were written for: G, and the units of the last tile (forward) where it is ragged
+PLAN_G = {(345, 4, 9, 3, 8, "u8", False, False): 2, (1537, 40, 40, 1, 32, "lens", False, False): 8,
+          (1300, 1, 20, 1, 16, "lens", False, True): 4, (3, 20, 20, 1, 8, "lens", False, False): 4}
+PLAN_TAIL = {(345, 3, 3, 3, 4, "lens", False, False): 1, (4099, 5, 5, 8, 4, "lens", False, False): 24}
+
+
+def test_the_appended_cases_are_the_planned_ones():
+    assert list(PLANS) == O.CASES[13:] and len(O.CASES) == 27
+    assert O.CASES[3][6] and O.CASES[5][1:3] == (4, 9) and O.WIDE[0] == O.CASES[11][0] == 131       # the cases used by index
+
+
+@pytest.mark.parametrize("args", list(PLANS), ids=O.sid)
+def test_pinned_plan(args):
+    B, Tq, Tk, H, hd = args[:5]
+    fwd, bwd = ops.seq_attn_plan(B, Tq, Tk, H, hd, False), ops.seq_attn_plan(B, Tq, Tk, H, hd, True)
+    assert ((fwd["TB"], fwd["nch"], fwd["CW"]), (bwd["TB"], bwd["nch"], bwd["CW"])) == PLANS[args]
+    assert fwd["G"] == bwd["G"] == PLAN_G.get(args, fwd["G"])
+    if args in PLAN_TAIL:
+        assert (B * H) % fwd["TB"] == PLAN_TAIL[args]
+
+
+def test_the_cases_reach_every_branch_of_the_plan():
+    """The union over `O.CASES` of what `O.plan_class` finds.  More than one unit per workgroup together with more than one
+    chunk is not asked for: it cannot occur (`test_plan_invariants_over_the_whole_envelope` asserts so)."""
+    reached = set().union(*(O.plan_class(args) for args in O.CASES))
+    wanted = {"TB=1", "1<TB<64", "TB=64", "TB fwd!=bwd", "nch=1", "nch=2", "nch=3", "nch fwd!=bwd", "last chunk cw%4!=0",
+              "G=1", "G=2", "G=4", "G=8", "shared, nch>1", "ragged last tile"}
+    assert wanted <= reached, sorted(wanted - reached)
+    assert O.plan_class(O.CASES[0]) == {"TB=1", "nch=1", "G=1"}
+    assert {"1<TB<64", "TB fwd!=bwd", "ragged last tile", "G=8"} <= O.plan_class(O.TILE_CLAMPED)
 
 
 def test_cpu_tensors_raise_no_cpu_fallback():

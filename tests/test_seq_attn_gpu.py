@@ -93,24 +93,120 @@ def test_empty_batch(dev):
 
 
 def test_two_runs_give_the_same_bits(dev):
-    c = O.case(*O.WIDE)
-    a, b = _run(dev, c), _run(dev, c)
-    for name in O.OUTPUTS:
-        assert torch.equal(a[name], b[name]), name
+    """One unit per workgroup, and 64 with a ragged last tile."""
+    for args in (O.WIDE, O.TILE_CAP):
+        c = O.case(*args)
+        a, b = _run(dev, c), _run(dev, c)
+        for name in O.OUTPUTS:
+            assert torch.equal(a[name], b[name]), (args, name)
 
 
-@pytest.mark.parametrize("args", [O.WIDE, O.CASES[11]], ids=O.sid)
+def _plans(shape, aligned=True):
+    """(forward, backward) plan of a call, from the launches' own arithmetic."""
+    return ops.seq_attn_plan(*shape, False, aligned), ops.seq_attn_plan(*shape, True, aligned)
+
+
+TILED = [O.TILE_MIXED, O.TILE_CAP, O.TILE_CAP_POOLED, O.TILE_CLAMPED]
+
+
+@pytest.mark.parametrize("args", [O.WIDE, O.CASES[11]] + TILED, ids=O.sid)
 def test_sample_alone_has_the_bits_it_has_in_the_batch(dev, args):
-    """Rows of the B = 131 cases (several samples per workgroup there) against their own B = 1 runs, and a ragged slice."""
+    """Samples of a batch against their own B = 1 runs, and a slice.  In the B = 131 cases every workgroup holds one unit (one
+    sample's head), so they compare grids only.  In the `TILED` cases a workgroup holds 2, 3 or 64 units, of several samples
+    with their own masks (and, in one, 3 units forward and 2 backward), and the B = 1 run holds one: the first sample, a
+    sample from the middle of a tile, the first sample of the last (ragged) tile in either direction, and the last sample."""
     c = O.case(*args)
+    B, _, _, H, _ = c["shape"]
+    fwd, bwd = _plans(c["shape"])
+    assert (fwd["TB"] > 1 and bwd["TB"] > 1) == (args in TILED) and (fwd["TB"] == 1 and bwd["TB"] == 1) == (args not in TILED)
+    assert all(p["TB"] == 1 for p in _plans((1,) + tuple(c["shape"][1:])))
+    samples = {0, B // 2, B - 1, max(1, fwd["TB"] // 2 // H)}
+    samples |= {(B * H - 1) // p["TB"] * p["TB"] // H for p in (fwd, bwd)}               # the owner of the last tile's first unit
     whole = _run(dev, c)
-    for b in (0, 64, 130):
+    for b in sorted(samples):
         one = _run(dev, O.slice_case(c, b, b + 1))
         for name in O.OUTPUTS:
             assert torch.equal(one[name], whole[name][b:b + 1]), (name, b)
     part = _run(dev, O.slice_case(c, 3, 30))
     for name in O.OUTPUTS:
         assert torch.equal(part[name], whole[name][3:30]), name
+
+
+def _padded(c, hd2):
+    """A one-head case with q, k, v and gout zero-padded to `hd2` columns, and the same scale."""
+    B, Tq, Tk, H, hd = c["shape"]
+    assert H == 1 and hd2 > hd and not c["shared"]
+    out = dict(c)
+    for name in ("q", "k", "v", "gout"):
+        out[name] = np.concatenate([c[name], np.zeros(c[name].shape[:2] + (hd2 - hd,), np.float32)], axis=2)
+    out["shape"] = (B, Tq, Tk, 1, hd2)
+    return out
+
+
+@pytest.mark.parametrize("widths", [(64, 128), (32, 64)], ids=str)
+def test_zero_columns_leave_the_bits(dev, widths):
+    """Padding every row with zero columns (same `scale`) moves the case to another chunking -- forward from 1 chunk to 2 and
+    backward from 2 to 3, or backward from 1 to 2 -- and only appends fmaf(0, 0, acc) to every score's chain: out, gq, gk and gv
+    keep their bits on the first columns and are 0 beyond.  This is what sees a partial sum that is carried from chunk to
+    chunk in another order, or the backward re-deriving P from a chunking that is not the forward's."""
+    hd, hd2 = widths
+    c = O.case(2, 64, 64, 1, hd, "lens", True, False)
+    wide = _padded(c, hd2)
+    nch = lambda shape: tuple(p["nch"] for p in _plans(shape))
+    assert (nch(c["shape"]), nch(wide["shape"])) == {(64, 128): ((1, 2), (2, 3)), (32, 64): ((1, 1), (1, 2))}[widths]
+    a, b = _run(dev, c), _run(dev, wide)
+    for name in O.OUTPUTS:
+        assert torch.equal(b[name][..., :hd], a[name]), name
+        assert bool((b[name][..., hd:] == 0).all()), name
+
+
+def _off_boundary(a, dev):
+    """The array as a contiguous device tensor that begins 4 bytes past a 16-byte boundary."""
+    if a is None:
+        return None
+    flat = torch.empty(a.size + 1, dtype=torch.float32, device=dev)
+    t = flat[1:].view(a.shape)
+    t.copy_(torch.from_numpy(np.ascontiguousarray(a)))
+    assert t.is_contiguous() and t.data_ptr() % 16 == 4
+    return t
+
+
+@pytest.mark.parametrize("args", [O.CHUNKED, O.U8_TILED], ids=O.sid)
+def test_rows_off_a_16_byte_boundary_give_the_same_bits(dev, args):
+    """hd % 4 == 0 with q, k, v and gout 4 bytes off a 16-byte boundary: the float-by-float path (`vec` 0), in two chunks and
+    in tiles of two units, has the bits of the 16-byte path."""
+    c = O.case(*args)
+    assert c["shape"][4] % 4 == 0 and all(p["vec"] == 1 for p in _plans(c["shape"]))
+    assert all(p["vec"] == 0 for p in _plans(c["shape"], aligned=False))
+    want = _run(dev, c)
+    q, k, v, gout = (_off_boundary(c[n], dev) for n in ("q", "k", "v", "gout"))
+    key_ok, lens = _dev(c["key_ok"], dev), _dev(c["lens"], dev)
+    out, saved = ops.seq_attn_fwd(q, k, v, c["H"], c["scale"], key_ok, lens, c["causal_or"])
+    gq, gk, gv = ops.seq_attn_bwd(q, k, v, c["H"], c["scale"], key_ok, lens, c["causal_or"], saved, gout)
+    for name, got in zip(O.OUTPUTS, (out, gq, gk, gv)):
+        assert torch.equal(got, want[name]), name
+
+
+def test_sample_with_nothing_allowed_inside_a_tile(dev):
+    """lens[5] = 0 in the case whose tiles of two units mix samples (the units of samples 4 and 5 share one): inside the rule
+    everywhere, the mean of v's rows for sample 5, and samples 4 and 6 keep the bits they have with lens[5] = 1."""
+    c1, c0 = dict(O.case(*O.TILE_MIXED)), dict(O.case(*O.TILE_MIXED))
+    B, Tq, Tk, H, hd = c0["shape"]
+    assert _plans(c0["shape"])[0]["TB"] == 2 and (4 * H + H - 1) // 2 == (5 * H) // 2      # sample 4's last unit, 5's first
+    for c, n in ((c1, 1), (c0, 0)):
+        c["lens"] = c["lens"].copy()
+        c["lens"][5] = n
+    s = np.einsum("ihc,jhc->hij", c0["q"][5].reshape(Tq, H, hd).astype(np.float64), c0["k"][5].reshape(Tk, H, hd)) * c0["scale"]
+    assert np.abs(s).max() < 32                               # -1e9 + S is -1e9 in f32: uniform weights
+    got0, got1 = _run(dev, c0), _run(dev, c1)
+    got = _np(got0)
+    O.check(got, c0, "all-masked-in-tile")
+    want = c0["v"][5].astype(np.float64).mean(0, keepdims=True).repeat(Tq, 0)
+    assert O.max_diff(got["out"][5], want) <= 1e-6
+    for name in O.OUTPUTS:
+        for b in (4, 6):
+            assert torch.equal(got0[name][b], got1[name][b]), (name, b)
+    assert not torch.equal(got0["out"][5], got1["out"][5])
 
 
 def test_argument_errors(dev):
