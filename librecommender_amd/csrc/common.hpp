@@ -34,6 +34,15 @@ inline int launch_status() {
 
 __host__ __device__ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// The smallest power of two >= x.  They differ only in their floor: next_pow2 starts at 1, ivf_pow2 at 2 (a bitonic sort of at
+// least one pair, whatever k is).
+inline int next_pow2(int x) {
+  int p = 1;
+  while (p < x) p <<= 1;
+  return p;
+}
+inline int ivf_pow2(int x) { return next_pow2(x < 2 ? 2 : x); }
+
 inline int grid_for(int64_t work_items, int items_per_block, int cap = kPersistentBlocks) {
   int64_t g = ceil_div(work_items, items_per_block);
   if (g < 1) g = 1;

@@ -12,17 +12,15 @@
 //               spreads over the chip.  A list that lies inside one chunk is summed and divided there; a list that crosses chunk
 //               borders leaves one partial sum per chunk and a second kernel adds them in chunk order (four interleaved slices,
 //               combined in slice order).  No floating-point atomics: the order of every sum is fixed by the shapes alone.
-//   search    : (1) coarse = lr_score_topk_f32(queries, centroids, k = nprobe): the nprobe best lists per query by (score desc,
-//               list id asc); (2) ivf_plan_kernel turns every (query, probed list) into ceil(len / CL) work items and scans the
-//               counts (one workgroup); (3) ivf_scan_kernel: a persistent grid of waves, one work item per wave at a time — the
-//               query sits in registers, list rows stream as float4 per lane (16 lanes per row, four rows per load), DPP reduce,
-//               survivors of the running threshold (and of the consumed filter) are appended to the wave's candidate list in LDS as
-//               64-bit (score, id) keys and the list is cut back to its k best by bisection when it fills (topk_keys.hpp); every
-//               work item leaves <= k keys; (4) ivf_merge_kernel: one workgroup per query streams its work items' keys through
-//               the same threshold / append / select scheme (one list per wave, then wave 0 folds the four) and sorts the k
-//               winners.  Order (score desc, id asc) is total, so the result does not depend on CL or on the grid.
-//               The plan, the DPP sum and the wave's running top-k are in ivf_common.hpp; the plan and merge kernels here also
-//               serve the int8 scan of ivf_sq8.hip through ivf_launch_plan / ivf_launch_merge.
+//   search    : the driver, the plan, the wave's running top-k and the scan kernel are ivf_common.hpp's (ivf_search: coarse =
+//               lr_score_topk_f32(queries, centroids, k = nprobe); plan; ivf_scan_kernel<Scorer>; merge).  This file supplies
+//               (1) FlatScorer<NCH>, the scan's row scorer: the query sits in registers, list rows stream as float4 per lane (16
+//               lanes per row, four rows per load, NCH chunks per lane), DPP reduce; (2) ivf_plan_kernel: every (query, probed
+//               list) becomes ceil(len / CL) work items and the counts are scanned (one workgroup); (3) ivf_merge_kernel: one
+//               workgroup per query streams its work items' keys through the scan's threshold / append / select scheme (one
+//               list per wave, then wave 0 folds the four) and sorts the k winners (topk_keys.hpp).  Order (score desc, id asc)
+//               is total, so the result does not depend on CL or on the grid.  The plan and merge kernels work on 64-bit keys
+//               only and serve every list format through ivf_launch_plan / ivf_launch_merge.
 #include <cstring>
 
 #include <rocprim/rocprim.hpp>
@@ -212,69 +210,33 @@ __global__ __launch_bounds__(1024) void ivf_plan_kernel(const int64_t* __restric
   if (tid == 1023) pref[P] = s_sum[1023];
 }
 
+// The f32 row scorer of the scan (ivf_common.hpp): 16 lanes per row, lane j holds the 16-byte chunks j + 16 c, c < NCH.
 template <int NCH>
-__global__ __launch_bounds__(kBlock) void ivf_scan_kernel(
-    const float* __restrict__ queries, int D, const int64_t* __restrict__ coarse_ids, int nprobe, int64_t P,
-    const int32_t* __restrict__ pref, const int64_t* __restrict__ list_ptr, const int32_t* __restrict__ list_ids,
-    const float* __restrict__ list_rows, const int64_t* __restrict__ consumed_ptr, const int32_t* __restrict__ consumed_idx,
-    const uint8_t* __restrict__ filter_flag, int k, int C, int CL, int64_t Wmax, uint64_t* __restrict__ part_keys,
-    int32_t* __restrict__ part_cnt) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wid = tid >> 6, j = lane & 15, g = lane >> 4;
-  const int D4 = D >> 2;
-  WaveTopk tk;
-  tk.L = reinterpret_cast<uint64_t*>(smem) + static_cast<size_t>(wid) * C;
-  tk.k = k;
-  tk.C = C;
-  tk.lane = lane;
-  const int64_t total = pref[P] < Wmax ? pref[P] : Wmax;      // (Wmax bounds it for every well-formed index)
-  for (int64_t w = static_cast<int64_t>(blockIdx.x) * 4 + wid; w < total; w += static_cast<int64_t>(gridDim.x) * 4) {
-    int64_t lo = 0, hi = P - 1;      // the pair of work item w: pref[pair] <= w < pref[pair + 1]
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (pref[mid + 1] > w) hi = mid; else lo = mid + 1;
-    }
-    const int64_t pair = lo, q = pair / nprobe, l = coarse_ids[pair];
-    const int64_t r0 = list_ptr[l] + (w - pref[pair]) * CL;
-    const int64_t r1 = list_ptr[l + 1] < r0 + CL ? list_ptr[l + 1] : r0 + CL;
-    float4 qv[NCH];
+struct FlatScorer {
+  static constexpr int RPW = 4;
+  static constexpr int PUSHES = 4;      // at most 16 keys a trip: one look at the room per trip (profiles/ivf_search_refactor.md)
+  const float* list_rows;
+  int D;
+  struct Query {
+    float4 v[NCH];
+  };
+  __device__ __forceinline__ Query load_query(const float* __restrict__ queries, int64_t q, int j) const {
+    Query qv;
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) qv[c] = (j + 16 * c) < D4 ? ld4(queries + q * D + (j + 16 * c) * 4) : f4_zero();
-    const bool flt = consumed_ptr != nullptr && (filter_flag == nullptr || filter_flag[q] != 0);
-    const int64_t clo = flt ? consumed_ptr[q] : 0, chi = flt ? consumed_ptr[q + 1] : 0;
-    tk.cnt = 0;
-    tk.T = 0ull;
-    for (int64_t r = r0; r < r1; r += 16) {
-      float sc[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int64_t row = r + u * 4 + g;
-        float p = 0.f;
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-          const int ch = j + 16 * c;
-          const float4 v = (row < r1 && ch < D4) ? ld4(list_rows + row * D + ch * 4) : f4_zero();
-          p = dot4(v, qv[c], p);
-        }
-        sc[u] = row16_sum(p);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int64_t row = r + u * 4 + g;
-        const bool ok = j == 0 && row < r1 && sc[u] == sc[u];      // NaN scores are dropped
-        const int32_t id = ok ? list_ids[row] : 0;
-        const uint64_t key = make_key(sc[u], static_cast<uint32_t>(id));
-        bool pass = ok && key > tk.T;
-        if (pass && flt) pass = !is_consumed(consumed_idx, clo, chi, id);
-        tk.push(pass, key);
-      }
-      if (tk.cnt + 16 > C) tk.shrink();
-    }
-    if (tk.cnt > k) tk.shrink();
-    for (int i = lane; i < tk.cnt; i += kWave) part_keys[w * k + i] = tk.L[i];
-    if (lane == 0) part_cnt[w] = tk.cnt;
+    for (int c = 0; c < NCH; ++c) qv.v[c] = (j + 16 * c) < (D >> 2) ? ld4(queries + q * D + (j + 16 * c) * 4) : f4_zero();
+    return qv;
   }
-}
+  __device__ __forceinline__ float score(const Query& qv, int64_t row, bool in_range, int j) const {
+    float p = 0.f;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int ch = j + 16 * c;
+      const float4 v = (in_range && ch < (D >> 2)) ? ld4(list_rows + row * D + ch * 4) : f4_zero();
+      p = dot4(v, qv.v[c], p);
+    }
+    return row16_sum(p);
+  }
+};
 
 __global__ __launch_bounds__(kBlock) void ivf_merge_kernel(const int32_t* __restrict__ pref, int nprobe,
                                                            const uint64_t* __restrict__ part_keys,
@@ -320,32 +282,8 @@ __global__ __launch_bounds__(kBlock) void ivf_merge_kernel(const int32_t* __rest
     for (int i = tk.cnt + lane; i < K2; i += kWave) tk.L[i] = 0ull;
   }
   __syncthreads();
-  uint64_t* a = s_keys;
-  for (int size = 2; size <= K2; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = tid; t < K2 / 2; t += kBlock) {
-        const int lo = 2 * t - (t & (stride - 1));
-        const int hi = lo + stride;
-        const bool desc = (lo & size) == 0;
-        const uint64_t x = a[lo], y = a[hi];
-        if (desc ? (x < y) : (x > y)) {
-          a[lo] = y;
-          a[hi] = x;
-        }
-      }
-      __syncthreads();
-    }
-  }
-  for (int r = tid; r < k; r += kBlock) {
-    const uint64_t e = a[r];
-    if (e == 0ull) {
-      out_scores[u * k + r] = -INFINITY;
-      out_ids[u * k + r] = -1;
-    } else {
-      out_scores[u * k + r] = fkey_inv(static_cast<uint32_t>(e >> 32));
-      out_ids[u * k + r] = static_cast<int64_t>(0xFFFFFFFFu - static_cast<uint32_t>(e));
-    }
-  }
+  block_sort_keys_desc(s_keys, K2, tid, kBlock);
+  emit_topk(s_keys, K2, k, u, 0, out_scores, out_ids, tid, kBlock);
 }
 
 void ivf_launch_plan(const IvfPlan& p, const int64_t* coarse_ids, const int64_t* list_ptr, int nlist, int32_t* pref, hipStream_t s) {
@@ -460,36 +398,10 @@ extern "C" int lr_ivf_search_f32(const float* queries, int64_t B, const float* c
                                  const int64_t* consumed_ptr, const int32_t* consumed_idx, const uint8_t* filter_flag, int k,
                                  int nprobe, float* out_scores, int64_t* out_ids, void* ws, size_t ws_bytes,
                                  lr_stream_t stream) {
-  LR_CHECK_ARG(B >= 0);
-  if (B == 0) return LR_OK;
-  const IvfPlan p = ivf_plan(B, N, D, k, nprobe, nlist);
-  if (!p.ok) return LR_ESHAPE;
-  LR_CHECK_ARG(queries && centroids && list_ptr && list_ids && list_rows && out_scores && out_ids);
-  LR_CHECK_ARG(reinterpret_cast<uintptr_t>(queries) % 16 == 0 && reinterpret_cast<uintptr_t>(centroids) % 16 == 0 &&
-               reinterpret_cast<uintptr_t>(list_rows) % 16 == 0);
-  if (ws == nullptr || ws_bytes < p.total) return LR_EWORKSPACE;
-  LR_CHECK_ARG(reinterpret_cast<uintptr_t>(ws) % 256 == 0);
-  hipStream_t s = as_stream(stream);
-  char* w = static_cast<char*>(ws);
-  float* cs = reinterpret_cast<float*>(w + p.off_cs);
-  int64_t* ci = reinterpret_cast<int64_t*>(w + p.off_ci);
-  int32_t* pref = reinterpret_cast<int32_t*>(w + p.off_pref);
-  int32_t* cnt = reinterpret_cast<int32_t*>(w + p.off_cnt);
-  uint64_t* keys = reinterpret_cast<uint64_t*>(w + p.off_keys);
-  int rc = lr_score_topk_f32(queries, B, centroids, nlist, D, nullptr, nullptr, nullptr, nprobe, 0, cs, ci, w + p.off_coarse,
-                             p.coarse_bytes, stream);
-  if (rc != LR_OK) return rc;
-  ivf_launch_plan(p, ci, list_ptr, nlist, pref, s);
-  const size_t lds = ivf_scan_lds(p);
-  const dim3 grid(grid_for(p.Wmax, 4)), block(kBlock);
-  const int nch = D <= 64 ? 1 : D <= 128 ? 2 : 4;
-#define LR_IVF_SCAN(NCH)                                                                                                       \
-  hipLaunchKernelGGL(ivf_scan_kernel<NCH>, grid, block, lds, s, queries, D, ci, nprobe, p.P, pref, list_ptr, list_ids, list_rows, \
-                     consumed_ptr, consumed_idx, filter_flag, k, p.C, p.CL, p.Wmax, keys, cnt)
-  if (nch == 1) LR_IVF_SCAN(1);
-  else if (nch == 2) LR_IVF_SCAN(2);
-  else LR_IVF_SCAN(4);
-#undef LR_IVF_SCAN
-  ivf_launch_merge(p, B, nprobe, k, pref, keys, cnt, out_scores, out_ids, s);
-  return launch_status();
+  return ivf_search(queries, B, centroids, nlist, list_ptr, list_ids, N, D, consumed_ptr, consumed_idx, filter_flag, k, nprobe,
+                    out_scores, out_ids, ws, ws_bytes, stream, true, ivf_rows_ptr_ok(list_rows), [&](auto launch) {
+                      if (D <= 64) launch(FlatScorer<1>{list_rows, D});
+                      else if (D <= 128) launch(FlatScorer<2>{list_rows, D});
+                      else launch(FlatScorer<4>{list_rows, D});
+                    });
 }

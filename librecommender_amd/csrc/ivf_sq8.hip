@@ -7,14 +7,13 @@
 //            gathered through list_ids): a = max |x| over the 16 lanes, scale = a / 127, code = clamp(rint(x / scale), -127, 127),
 //            division and rounding by intrinsics so that nothing contracts.  A lane writes its 16 codes with one 16-byte store;
 //            columns from D up to the stored stride are code 0.  a == 0 gives scale 0 and codes 0.
-//   search : coarse top-nprobe, the work plan and the merge are the Flat search's (ivf_common.hpp).  ivf_sq8_scan_kernel is its
-//            scan over codes: a code row is `stride` bytes (D rounded up to 16), LPR = next_pow2(stride / 16) lanes share a row and
+//   search : the whole search but the scoring of a row is ivf_common.hpp's (ivf_search, ivf_scan_kernel<Scorer>).  Sq8Scorer<LPR>
+//            scores code rows: a row is `stride` bytes (D rounded up to 16), LPR = next_pow2(stride / 16) lanes share a row and
 //            each loads 16 codes with one 16-byte load, so a wave-load covers 64 / LPR rows; the f32 query slice of the lane sits in
 //            registers; dot = 16 fmas in column order, then log2(LPR) DPP pair sums; score = scale * dot, one rounded multiply.
-//            Survivors of the running threshold and of the consumed filter enter the wave's candidate list as 64-bit keys.
 //   rerank : ivf_rerank_kernel.  One workgroup per query: every 16-lane group gathers a candidate's f32 row by global id and
-//            takes the f32 inner product (fma chains, DPP sum), ids of -1 are skipped; the keys are sorted in LDS (bitonic) and
-//            the k best written, -1 / -inf beyond them.
+//            takes the f32 inner product (fma chains, DPP sum), ids of -1 are skipped; the keys are sorted in LDS and the k best
+//            written, -1 / -inf beyond them (topk_keys.hpp).
 // No floating-point atomics: two calls give the same bits.
 #include "common.hpp"
 #include "ivf_common.hpp"
@@ -81,70 +80,35 @@ __device__ __forceinline__ float sq8_dot4(uint32_t w, float4 q, float p) {
   return fmaf(static_cast<float>(static_cast<int32_t>(w) >> 24), q.w, p);
 }
 
+// The code row scorer of the scan (ivf_common.hpp): LPR lanes per row, lane j holds columns [16 j, 16 j + 16) as one 16-byte load.
 template <int LPR>
-__global__ __launch_bounds__(kBlock) void ivf_sq8_scan_kernel(
-    const float* __restrict__ queries, int D, const int64_t* __restrict__ coarse_ids, int nprobe, int64_t P,
-    const int32_t* __restrict__ pref, const int64_t* __restrict__ list_ptr, const int32_t* __restrict__ list_ids,
-    const int8_t* __restrict__ codes, int stride, const float* __restrict__ scales, const int64_t* __restrict__ consumed_ptr,
-    const int32_t* __restrict__ consumed_idx, const uint8_t* __restrict__ filter_flag, int k, int C, int CL, int64_t Wmax,
-    uint64_t* __restrict__ part_keys, int32_t* __restrict__ part_cnt) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int RPW = kWave / LPR;      // rows of one wave-load
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wid = tid >> 6, j = lane & (LPR - 1), g = lane / LPR;
-  const bool mine = 16 * j < stride;      // LPR is a power of two: the lanes past the row's last chunk load nothing
-  WaveTopk tk;
-  tk.L = reinterpret_cast<uint64_t*>(smem) + static_cast<size_t>(wid) * C;
-  tk.k = k;
-  tk.C = C;
-  tk.lane = lane;
-  const int64_t total = pref[P] < Wmax ? pref[P] : Wmax;      // (Wmax bounds it for every well-formed index)
-  for (int64_t w = static_cast<int64_t>(blockIdx.x) * 4 + wid; w < total; w += static_cast<int64_t>(gridDim.x) * 4) {
-    int64_t lo = 0, hi = P - 1;      // the pair of work item w: pref[pair] <= w < pref[pair + 1]
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (pref[mid + 1] > w) hi = mid; else lo = mid + 1;
-    }
-    const int64_t pair = lo, q = pair / nprobe, l = coarse_ids[pair];
-    const int64_t r0 = list_ptr[l] + (w - pref[pair]) * CL;
-    const int64_t r1 = list_ptr[l + 1] < r0 + CL ? list_ptr[l + 1] : r0 + CL;
-    float4 qv[4];
+struct Sq8Scorer {
+  static constexpr int RPW = kWave / LPR;
+  static constexpr int PUSHES = 1;      // up to 64 keys per wave-load
+  const int8_t* codes;
+  int stride;
+  const float* scales;
+  int D;
+  struct Query {
+    float4 v[4];
+  };
+  __device__ __forceinline__ Query load_query(const float* __restrict__ queries, int64_t q, int j) const {
+    Query qv;
 #pragma unroll
-    for (int c = 0; c < 4; ++c) qv[c] = (16 * j + 4 * c) < D ? ld4(queries + q * D + 16 * j + 4 * c) : f4_zero();
-    const bool flt = consumed_ptr != nullptr && (filter_flag == nullptr || filter_flag[q] != 0);
-    const int64_t clo = flt ? consumed_ptr[q] : 0, chi = flt ? consumed_ptr[q + 1] : 0;
-    tk.cnt = 0;
-    tk.T = 0ull;
-    for (int64_t r = r0; r < r1; r += 4 * RPW) {
-      float sc[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int64_t row = r + u * RPW + g;
-        const bool in = row < r1;
-        const uint4 v = (in && mine) ? *reinterpret_cast<const uint4*>(codes + row * stride + 16 * j) : make_uint4(0u, 0u, 0u, 0u);
-        const float scale = (in && j == 0) ? scales[row] : 0.f;
-        float p = sq8_dot4(v.x, qv[0], 0.f);
-        p = sq8_dot4(v.y, qv[1], p);
-        p = sq8_dot4(v.z, qv[2], p);
-        p = sq8_dot4(v.w, qv[3], p);
-        sc[u] = __fmul_rn(scale, sq8_lanes_sum<LPR>(p));
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int64_t row = r + u * RPW + g;
-        const bool ok = j == 0 && row < r1 && sc[u] == sc[u];      // NaN scores are dropped
-        const int32_t id = ok ? list_ids[row] : 0;
-        const uint64_t key = make_key(sc[u], static_cast<uint32_t>(id));
-        bool pass = ok && key > tk.T;
-        if (pass && flt) pass = !is_consumed(consumed_idx, clo, chi, id);
-        tk.push(pass, key);      // at most RPW lanes pass
-        if (tk.cnt + RPW > C) tk.shrink();
-      }
-    }
-    if (tk.cnt > k) tk.shrink();
-    for (int i = lane; i < tk.cnt; i += kWave) part_keys[w * k + i] = tk.L[i];
-    if (lane == 0) part_cnt[w] = tk.cnt;
+    for (int c = 0; c < 4; ++c) qv.v[c] = (16 * j + 4 * c) < D ? ld4(queries + q * D + 16 * j + 4 * c) : f4_zero();
+    return qv;
   }
-}
+  __device__ __forceinline__ float score(const Query& qv, int64_t row, bool in_range, int j) const {
+    const bool mine = 16 * j < stride;      // LPR is a power of two: the lanes past the row's last chunk load nothing
+    const uint4 v = (in_range && mine) ? *reinterpret_cast<const uint4*>(codes + row * stride + 16 * j) : make_uint4(0u, 0u, 0u, 0u);
+    const float scale = (in_range && j == 0) ? scales[row] : 0.f;
+    float p = sq8_dot4(v.x, qv.v[0], 0.f);
+    p = sq8_dot4(v.y, qv.v[1], p);
+    p = sq8_dot4(v.z, qv.v[2], p);
+    p = sq8_dot4(v.w, qv.v[3], p);
+    return __fmul_rn(scale, sq8_lanes_sum<LPR>(p));
+  }
+};
 
 // ---- re-rank ------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void ivf_rerank_kernel(const float* __restrict__ queries, const float* __restrict__ rows,
@@ -172,31 +136,8 @@ __global__ __launch_bounds__(kBlock) void ivf_rerank_kernel(const float* __restr
     if (j == 0 && ci < K2) a[ci] = (live && p == p) ? make_key(p, static_cast<uint32_t>(id)) : 0ull;
   }
   __syncthreads();
-  for (int size = 2; size <= K2; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = tid; t < K2 / 2; t += kBlock) {
-        const int lo = 2 * t - (t & (stride - 1));
-        const int hi = lo + stride;
-        const bool desc = (lo & size) == 0;
-        const uint64_t x = a[lo], y = a[hi];
-        if (desc ? (x < y) : (x > y)) {
-          a[lo] = y;
-          a[hi] = x;
-        }
-      }
-      __syncthreads();
-    }
-  }
-  for (int r = tid; r < k; r += kBlock) {
-    const uint64_t e = r < K2 ? a[r] : 0ull;
-    if (e == 0ull) {
-      out_scores[u * k + r] = -INFINITY;
-      out_ids[u * k + r] = -1;
-    } else {
-      out_scores[u * k + r] = fkey_inv(static_cast<uint32_t>(e >> 32));
-      out_ids[u * k + r] = static_cast<int64_t>(0xFFFFFFFFu - static_cast<uint32_t>(e));
-    }
-  }
+  block_sort_keys_desc(a, K2, tid, kBlock);
+  emit_topk(a, K2, k, u, 0, out_scores, out_ids, tid, kBlock);
 }
 
 static inline bool sq8_stride_ok(int D, int stride) { return stride >= D && stride <= 256 && (stride % 16) == 0; }
@@ -234,40 +175,16 @@ extern "C" int lr_ivf_sq8_search_f32(const float* queries, int64_t B, const floa
                                      int D, const int64_t* consumed_ptr, const int32_t* consumed_idx, const uint8_t* filter_flag,
                                      int kk, int nprobe, float* out_scores, int64_t* out_ids, void* ws, size_t ws_bytes,
                                      lr_stream_t stream) {
-  LR_CHECK_ARG(B >= 0);
-  if (B == 0) return LR_OK;
-  const IvfPlan p = ivf_plan(B, N, D, kk, nprobe, nlist);
-  if (!p.ok || !sq8_stride_ok(D, code_stride)) return LR_ESHAPE;
-  LR_CHECK_ARG(queries && centroids && list_ptr && list_ids && codes && scales && out_scores && out_ids);
-  LR_CHECK_ARG(reinterpret_cast<uintptr_t>(queries) % 16 == 0 && reinterpret_cast<uintptr_t>(centroids) % 16 == 0 &&
-               reinterpret_cast<uintptr_t>(codes) % 16 == 0);
-  if (ws == nullptr || ws_bytes < p.total) return LR_EWORKSPACE;
-  LR_CHECK_ARG(reinterpret_cast<uintptr_t>(ws) % 256 == 0);
-  hipStream_t s = as_stream(stream);
-  char* w = static_cast<char*>(ws);
-  float* cs = reinterpret_cast<float*>(w + p.off_cs);
-  int64_t* ci = reinterpret_cast<int64_t*>(w + p.off_ci);
-  int32_t* pref = reinterpret_cast<int32_t*>(w + p.off_pref);
-  int32_t* cnt = reinterpret_cast<int32_t*>(w + p.off_cnt);
-  uint64_t* keys = reinterpret_cast<uint64_t*>(w + p.off_keys);
-  int rc = lr_score_topk_f32(queries, B, centroids, nlist, D, nullptr, nullptr, nullptr, nprobe, 0, cs, ci, w + p.off_coarse,
-                             p.coarse_bytes, stream);
-  if (rc != LR_OK) return rc;
-  ivf_launch_plan(p, ci, list_ptr, nlist, pref, s);
-  const size_t lds = ivf_scan_lds(p);
-  const dim3 grid(grid_for(p.Wmax, 4)), block(kBlock);
   const int chunks = code_stride / 16;
-#define LR_SQ8_SCAN(LPR)                                                                                                          \
-  hipLaunchKernelGGL(ivf_sq8_scan_kernel<LPR>, grid, block, lds, s, queries, D, ci, nprobe, p.P, pref, list_ptr, list_ids, codes, \
-                     code_stride, scales, consumed_ptr, consumed_idx, filter_flag, kk, p.C, p.CL, p.Wmax, keys, cnt)
-  if (chunks == 1) LR_SQ8_SCAN(1);
-  else if (chunks == 2) LR_SQ8_SCAN(2);
-  else if (chunks <= 4) LR_SQ8_SCAN(4);
-  else if (chunks <= 8) LR_SQ8_SCAN(8);
-  else LR_SQ8_SCAN(16);
-#undef LR_SQ8_SCAN
-  ivf_launch_merge(p, B, nprobe, kk, pref, keys, cnt, out_scores, out_ids, s);
-  return launch_status();
+  return ivf_search(queries, B, centroids, nlist, list_ptr, list_ids, N, D, consumed_ptr, consumed_idx, filter_flag, kk, nprobe,
+                    out_scores, out_ids, ws, ws_bytes, stream, sq8_stride_ok(D, code_stride), ivf_rows_ptr_ok(codes) && scales,
+                    [&](auto launch) {
+                      if (chunks == 1) launch(Sq8Scorer<1>{codes, code_stride, scales, D});
+                      else if (chunks == 2) launch(Sq8Scorer<2>{codes, code_stride, scales, D});
+                      else if (chunks <= 4) launch(Sq8Scorer<4>{codes, code_stride, scales, D});
+                      else if (chunks <= 8) launch(Sq8Scorer<8>{codes, code_stride, scales, D});
+                      else launch(Sq8Scorer<16>{codes, code_stride, scales, D});
+                    });
 }
 
 extern "C" int lr_ivf_rerank_f32(const float* queries, int64_t B, const float* rows, int64_t N, int D, const int64_t* cand_ids,

@@ -845,35 +845,12 @@ __global__ __launch_bounds__(NT) void topk_merge_keys_kernel(
       if (slot < K2) a[slot] = e[c];
     }
   __syncthreads();
-  for (int size = 2; size <= K2; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = tid; t < K2 / 2; t += NT) {
-        const int lo = 2 * t - (t & (stride - 1));
-        const int hi = lo + stride;
-        const bool desc = (lo & size) == 0;
-        const uint64_t x = a[lo], y = a[hi];
-        if (desc ? (x < y) : (x > y)) {
-          a[lo] = y;
-          a[hi] = x;
-        }
-      }
-      __syncthreads();
-    }
-  }
+  block_sort_keys_desc(a, K2, tid, NT);
   if (keys_out != nullptr) {
     for (int r = tid; r < k; r += NT) keys_out[(static_cast<int64_t>(blockIdx.y) * B_pad + u) * k + r] = a[r];
     return;
   }
-  for (int r = tid; r < k; r += NT) {
-    const uint64_t w = a[r];
-    if (w == 0ull) {
-      out_scores[u * k + r] = -INFINITY;
-      out_ids[u * k + r] = -1;
-    } else {
-      out_scores[u * k + r] = fkey_inv(static_cast<uint32_t>(w >> 32));
-      out_ids[u * k + r] = item_base + static_cast<int64_t>(0xFFFFFFFFu - static_cast<uint32_t>(w));
-    }
-  }
+  emit_topk(a, K2, k, u, item_base, out_scores, out_ids, tid, NT);
 }
 
 // merge of already-final (score, global id) lists from S shards: re-key, then same sort.
@@ -935,12 +912,6 @@ __global__ __launch_bounds__(kBlock) void topk_merge_pairs_kernel(
       out_ids[u * k + r] = static_cast<int64_t>(~idk[r]);
     }
   }
-}
-
-static inline int next_pow2(int x) {
-  int p = 1;
-  while (p < x) p <<= 1;
-  return p;
 }
 
 // test hook (lr_score_topk_test_mute): the user-tile workgroup that never publishes its progress word; -1 = none
@@ -1200,31 +1171,8 @@ __global__ __launch_bounds__(kBlock) void topk_rescore_kernel(
     if (gl == 0) a[c] = key;
   }
   __syncthreads();
-  for (int size = 2; size <= K2; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = tid; t < K2 / 2; t += kBlock) {
-        const int lo = 2 * t - (t & (stride - 1));
-        const int hi = lo + stride;
-        const bool desc = (lo & size) == 0;
-        const uint64_t x = a[lo], y = a[hi];
-        if (desc ? (x < y) : (x > y)) {
-          a[lo] = y;
-          a[hi] = x;
-        }
-      }
-      __syncthreads();
-    }
-  }
-  for (int r = tid; r < k; r += kBlock) {
-    const uint64_t w = a[r];
-    if (w == 0ull) {
-      out_scores[u * k + r] = -INFINITY;
-      out_ids[u * k + r] = -1;
-    } else {
-      out_scores[u * k + r] = fkey_inv(static_cast<uint32_t>(w >> 32));
-      out_ids[u * k + r] = item_base + static_cast<int64_t>(0xFFFFFFFFu - static_cast<uint32_t>(w));
-    }
-  }
+  block_sort_keys_desc(a, K2, tid, kBlock);
+  emit_topk(a, K2, k, u, item_base, out_scores, out_ids, tid, kBlock);
   if (tid == 0) {
     const bool full = a_ids[u * kp + kp - 1] >= 0;            // the approximate pass filled its list: items exist outside it
     bool ok = *maxn2 == 0u && !user_bad;                      // (a row with a non-finite norm: no bound, nobody is certified)

@@ -1,7 +1,8 @@
-// Order-preserving (score, id) keys and the wave-level selection over lists of them, shared by the full-catalogue scan
-// (score_topk.hip) and the inverted-file scan (ivf.hip).  A key is (score bits made monotone << 32) | ~id: larger key = larger
-// score, then smaller id — a total order, so a result does not depend on the tiling that produced its candidates.  0 is never a
-// key of a finite or infinite score and marks an empty slot.
+// Order-preserving (score, id) keys, the wave-level selection over lists of them and the workgroup's final sort and write-out,
+// shared by the full-catalogue scan (score_topk.hip) and the inverted-file search (ivf_common.hpp, ivf.hip, ivf_sq8.hip).  A
+// key is (score bits made monotone << 32) | ~id: larger key = larger score, then smaller id — a total order, so a result does
+// not depend on the tiling that produced its candidates.  0 is never a key of a finite or infinite score and marks an empty
+// slot.
 #pragma once
 #include "common.hpp"
 
@@ -47,6 +48,42 @@ __device__ __forceinline__ int wave_compact(uint64_t* L, int cnt, uint64_t T, in
     base += __popcll(mask);
   }
   return base;
+}
+
+// bitonic sort of a[0..K2) in LDS, descending, by the whole workgroup (K2 a power of two; empty slots, 0, end up last).  The
+// caller's barrier after filling `a` comes before the call; the sort ends with one.
+__device__ __forceinline__ void block_sort_keys_desc(uint64_t* a, int K2, int tid, int nthreads) {
+  for (int size = 2; size <= K2; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int t = tid; t < K2 / 2; t += nthreads) {
+        const int lo = 2 * t - (t & (stride - 1));
+        const int hi = lo + stride;
+        const bool desc = (lo & size) == 0;
+        const uint64_t x = a[lo], y = a[hi];
+        if (desc ? (x < y) : (x > y)) {
+          a[lo] = y;
+          a[hi] = x;
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// out_scores / out_ids [row * k ..): the first k of the sorted keys a[0..avail) as (score, id_base + id); -inf / -1 where the
+// slot is empty or beyond `avail`
+__device__ __forceinline__ void emit_topk(const uint64_t* a, int avail, int k, int64_t row, int64_t id_base,
+                                          float* __restrict__ out_scores, int64_t* __restrict__ out_ids, int tid, int nthreads) {
+  for (int r = tid; r < k; r += nthreads) {
+    const uint64_t e = r < avail ? a[r] : 0ull;
+    if (e == 0ull) {
+      out_scores[row * k + r] = -INFINITY;
+      out_ids[row * k + r] = -1;
+    } else {
+      out_scores[row * k + r] = fkey_inv(static_cast<uint32_t>(e >> 32));
+      out_ids[row * k + r] = id_base + static_cast<int64_t>(0xFFFFFFFFu - static_cast<uint32_t>(e));
+    }
+  }
 }
 
 __device__ __forceinline__ bool is_consumed(const int32_t* __restrict__ ci, int64_t lo, int64_t hi,

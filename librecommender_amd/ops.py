@@ -1115,6 +1115,32 @@ def _ivf_check_width(D: int, what: str) -> None:
         raise ValueError(f"{what}: shape not supported (row width {D} outside 1..256)")
 
 
+def _topk_out(out: Optional[tuple], B: int, k: int, dev, what: str):
+    """The (scores [B, k] f32, ids [B, k] int64) pair a search writes: new tensors, or the caller's `out` after its checks (`what`
+    is the name of k in the error)."""
+    if out is None:
+        return torch.empty((B, k), dtype=torch.float32, device=dev), torch.empty((B, k), dtype=torch.int64, device=dev)
+    out_s, out_i = _req(out[0], torch.float32, "out scores", 2), _req(out[1], torch.int64, "out ids", 2)
+    if tuple(out_s.shape) != (B, k) or tuple(out_i.shape) != (B, k):
+        raise ValueError(f"out must be ([B, {what}] f32, [B, {what}] int64)")
+    return out_s, out_i
+
+
+def _ivf_search_common(queries, centroids, lists, list_ptr, list_ids, consumed_ptr, consumed_idx, filter_flag) -> None:
+    """Device, dtype and rank checks of a search's tensors; `lists` is the format's own payload as (tensor, dtype, name, rank)."""
+    _req(queries, torch.float32, "queries", 2)
+    _req(centroids, torch.float32, "centroids", 2)
+    for t, dtype, name, rank in lists:
+        _req(t, dtype, name, rank)
+    _req(list_ptr, torch.int64, "list_ptr", 1)
+    _req(list_ids, torch.int32, "list_ids", 1)
+    if consumed_ptr is not None:
+        _req(consumed_ptr, torch.int64, "consumed_ptr", 1)
+        _req(consumed_idx, torch.int32, "consumed_idx", 1)
+    if filter_flag is not None:
+        _req(filter_flag, torch.uint8, "filter_flag", 1)
+
+
 def ivf_assign(rows: torch.Tensor, centroids: torch.Tensor, want_score: bool = False):
     """int32 [n]: for every row the centroid of largest inner product, ties to the lowest list id (`lr_ivf_assign_f32`);
     with `want_score` also that inner product."""
@@ -1208,25 +1234,11 @@ def ivf_search(queries: torch.Tensor, centroids: torch.Tensor, list_ptr: torch.T
     lib = _lib.load()
     if B > 0 and not lib.lr_ivf_supported(B, N, Dp, k, nprobe, nlist):
         raise ValueError(f"ivf_search: shape not supported (B={B} N={N} D={D} k={k} nprobe={nprobe} nlist={nlist})")
-    _req(queries, torch.float32, "queries", 2)
-    _req(centroids, torch.float32, "centroids", 2)
-    _req(list_rows, torch.float32, "list_rows", 2)
-    _req(list_ptr, torch.int64, "list_ptr", 1)
-    _req(list_ids, torch.int32, "list_ids", 1)
-    if consumed_ptr is not None:
-        _req(consumed_ptr, torch.int64, "consumed_ptr", 1)
-        _req(consumed_idx, torch.int32, "consumed_idx", 1)
-    if filter_flag is not None:
-        _req(filter_flag, torch.uint8, "filter_flag", 1)
+    _ivf_search_common(queries, centroids, [(list_rows, torch.float32, "list_rows", 2)], list_ptr, list_ids, consumed_ptr,
+                       consumed_idx, filter_flag)
     queries, centroids, list_rows = _ivf_pad(queries, centroids, list_rows)
     dev = queries.device
-    if out is None:
-        out_s = torch.empty((B, k), dtype=torch.float32, device=dev)
-        out_i = torch.empty((B, k), dtype=torch.int64, device=dev)
-    else:
-        out_s, out_i = _req(out[0], torch.float32, "out scores", 2), _req(out[1], torch.int64, "out ids", 2)
-        if tuple(out_s.shape) != (B, k) or tuple(out_i.shape) != (B, k):
-            raise ValueError("out must be ([B, k] f32, [B, k] int64)")
+    out_s, out_i = _topk_out(out, B, k, dev, "k")
     if B == 0:
         return out_s, out_i
     ws = torch.empty(lib.lr_ivf_search_ws_bytes(B, N, Dp, k, nprobe, nlist), dtype=torch.uint8, device=dev)
@@ -1305,26 +1317,11 @@ def ivf_sq8_search(queries: torch.Tensor, centroids: torch.Tensor, list_ptr: tor
     ws_bytes = lib.lr_ivf_sq8_search_ws_bytes(B, N, Dp, kk, nprobe, nlist) if B > 0 else 0
     if B > 0 and ws_bytes == 0:
         raise ValueError(f"ivf_sq8_search: shape not supported (B={B} N={N} D={D} kk={kk} nprobe={nprobe} nlist={nlist})")
-    _req(queries, torch.float32, "queries", 2)
-    _req(centroids, torch.float32, "centroids", 2)
-    _req(codes, torch.int8, "codes", 2)
-    _req(scales, torch.float32, "scales", 1)
-    _req(list_ptr, torch.int64, "list_ptr", 1)
-    _req(list_ids, torch.int32, "list_ids", 1)
-    if consumed_ptr is not None:
-        _req(consumed_ptr, torch.int64, "consumed_ptr", 1)
-        _req(consumed_idx, torch.int32, "consumed_idx", 1)
-    if filter_flag is not None:
-        _req(filter_flag, torch.uint8, "filter_flag", 1)
+    _ivf_search_common(queries, centroids, [(codes, torch.int8, "codes", 2), (scales, torch.float32, "scales", 1)], list_ptr,
+                       list_ids, consumed_ptr, consumed_idx, filter_flag)
     queries, centroids = _ivf_pad(queries, centroids)
     dev = queries.device
-    if out is None:
-        out_s = torch.empty((B, kk), dtype=torch.float32, device=dev)
-        out_i = torch.empty((B, kk), dtype=torch.int64, device=dev)
-    else:
-        out_s, out_i = _req(out[0], torch.float32, "out scores", 2), _req(out[1], torch.int64, "out ids", 2)
-        if tuple(out_s.shape) != (B, kk) or tuple(out_i.shape) != (B, kk):
-            raise ValueError("out must be ([B, kk] f32, [B, kk] int64)")
+    out_s, out_i = _topk_out(out, B, kk, dev, "kk")
     if B == 0:
         return out_s, out_i
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
@@ -1350,14 +1347,7 @@ def ivf_rerank(queries: torch.Tensor, rows: torch.Tensor, cand_ids: torch.Tensor
     _req(rows, torch.float32, "rows", 2)
     _req(cand_ids, torch.int64, "cand_ids", 2)
     queries, rows = _ivf_pad(queries, rows)
-    dev = queries.device
-    if out is None:
-        out_s = torch.empty((B, k), dtype=torch.float32, device=dev)
-        out_i = torch.empty((B, k), dtype=torch.int64, device=dev)
-    else:
-        out_s, out_i = _req(out[0], torch.float32, "out scores", 2), _req(out[1], torch.int64, "out ids", 2)
-        if tuple(out_s.shape) != (B, k) or tuple(out_i.shape) != (B, k):
-            raise ValueError("out must be ([B, k] f32, [B, k] int64)")
+    out_s, out_i = _topk_out(out, B, k, queries.device, "k")
     if B == 0:
         return out_s, out_i
     _call("lr_ivf_rerank_f32", _ptr(queries), B, _ptr(rows), N, rows.shape[1], _ptr(cand_ids), kk, k, _ptr(out_s), _ptr(out_i),

@@ -142,7 +142,7 @@ def _index_items(path: str, model, nlist, nprobe):
     """The f32 item rows an index file is built over, after the argument checks that need no device."""
     import torch
 
-    from ..recommendation.ivf import check_train_args
+    from ..recommendation.ivf import _IVFIndex
 
     _ensure_dir(path)
     items = model.item_embeds
@@ -150,7 +150,5 @@ def _index_items(path: str, model, nlist, nprobe):
         items = items.gather()                    # sharded export: assembled on request
     assert items is not None, "call `model.fit()` before saving the index"
     items = items[: model.n_items]
-    check_train_args(items.shape[0], items.shape[1], int(nlist), 20)
-    if not 1 <= int(nprobe) <= int(nlist):
-        raise ValueError(f"nprobe must be in 1..nlist ({nlist}), got {nprobe}")
+    _IVFIndex.check_train_args(items.shape[0], items.shape[1], int(nlist), 20, nprobe)
     return items.to(torch.float32).contiguous()

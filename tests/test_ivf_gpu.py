@@ -145,6 +145,11 @@ SEARCH_CASES = [
     (5000, 7, 128, 1, 100, 7, "skew"),
     (1000, 80, 6, 3, 1024, 80, "assign"),       # nprobe * k = 81,920 > 8,192 and k > N, through the host pad
     (5000, 80, 128, 1, 1024, 10, "assign"),     # nprobe * k = 10,240 > 8,192
+    # widths between the others: (SQ8 stride and lanes per row | Flat chunks per lane)
+    (1000, 7, 40, 3, 10, 3, "assign"),          # 48: 4 lanes, one idle | 1 chunk, ragged
+    (1000, 7, 64, 3, 10, 3, "assign"),          # 64: 4 lanes, all busy | 1 chunk, full
+    (1000, 7, 100, 3, 10, 3, "assign"),         # 112: 8 lanes, one idle | 2 chunks, ragged
+    (1000, 7, 200, 3, 10, 3, "assign"),         # 208: 16 lanes, three idle | 4 chunks, ragged
 ]
 
 
